@@ -1,6 +1,6 @@
 """bench.py -- UniDistill distillation training on MI355X: one JSON line per run (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full distillation training step (student fwd + frozen-teacher fwd + detection and
@@ -9,12 +9,16 @@ nuScenes-shaped input.  The path is pure data parallel: every ran
 own samples and gradients are averaged with RCCL, so `scaling` is "weak" and
 value = samples of all ranks / max-over-ranks wall time.
 
-HEADLINE = fp32, the reference's arithmetic (it has no autocast anywhere: base_cli.py:40-45); the bf16
-mixed-precision step (BASELINE.json configs[4] style) is timed afterwards with its own trainer and reported
-as the labelled object `bf16_mixed_precision` -- never as `value`.
+HEADLINE = fp32, the reference's arithmetic (it has no autocast anywhere: base_cli.py:40-45).  A plain run
+sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints
+the line.  --dump-outputs DIR writes what rank 0's last timed step computed as DIR/<name>.npy: the loss and
+the loss terms the step returns, plus a fixed, seeded sample of the updated parameters and of their
+gradients (float32 / float64, a few MB).  Inputs and initial weights are seeded: the same arguments give the
+same inputs on every run.
 
-After the timed region (never counted in `value`) further legs run:
-  * bf16_mixed_precision (all ranks): the same workload under bf16 autocast + channels-last;
+With --full (off by default) further legs run after the timed region, never counted in `value`:
+  * bf16_mixed_precision (all ranks): the same workload under bf16 autocast + channels-last (BASELINE.json
+    configs[4] style), timed with its own trainer and reported as this labelled object -- never as `value`;
   * roofline (rank 0): the reference-boundary bev_pool forward (BASELINE.json: "bev_pool+voxelize HBM GB/s")
     at the BASELINE shape, its dominant kernel timed with HIP events on its launch stream, plus the
     op-level and counter-byte fractions; roofline_voxelize: ud_voxelize at 30 k and 4 x 300 k points;
@@ -29,6 +33,7 @@ After the timed region (never counted in `value`) further legs run:
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -79,11 +84,21 @@ def parse():
     ap.add_argument("--autocast", default="none", choices=["none", "bf16"],
                     help="precision of the HEADLINE: none = fp32 (the reference's arithmetic, default); bf16 = "
                          "mixed precision as the headline (then no second leg)")
-    ap.add_argument("--no-bf16-leg", action="store_true", help="skip the bf16 mixed-precision leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the bf16 leg, the roofline / MFMA / sparse-conv legs, the host "
+                         "enqueue leg and the CPU baseline (off by default: a plain run only times the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-bf16-leg", action="store_true", help="with --full: skip the bf16 mixed-precision leg")
     ap.add_argument("--nchw", action="store_true", help="keep dense convs NCHW (default: channels-last)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline / MFMA / host legs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                 # a plain run measures the headline only
+        args.no_bf16_leg = args.no_cpu_baseline = args.no_roofline = True
+    return args
 
 
 def roofline_leg(device, batch):
@@ -579,7 +594,33 @@ def timed_steps(trainer, batch, args, world, device):
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt, loss
+    return dt, loss, out
+
+
+DUMP_SAMPLE = 1 << 20     # elements of the parameter / gradient samples (4 MB each as float32)
+
+
+def dump_outputs(trainer, out, path):
+    """What the caller of the timed step receives from its last call: `loss` and the loss terms (`tb`), and the state the
+    step leaves behind -- the updated trainable parameters and their gradients, as a fixed, seeded sample of the
+    concatenated flat tensors (the same indices on every run with the same arguments).  Written as <path>/<name>.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": out["loss"]}
+    for k, v in sorted(out.get("tb", {}).items()):
+        if torch.is_tensor(v) or isinstance(v, (int, float)):
+            arrays["tb_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k)] = v      # keys such as "task_0/box_loss"
+    params = trainer.params
+    total = sum(p.numel() for p in params)
+    idx = np.sort(np.random.default_rng(0).choice(total, size=min(total, DUMP_SAMPLE), replace=False))
+    idx_d = torch.from_numpy(idx).to(params[0].device)
+    with torch.no_grad():
+        arrays["param_sample"] = torch.cat([p.detach().reshape(-1).float() for p in params])[idx_d]
+        arrays["grad_sample"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                           for p in params])[idx_d]
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(path, name + ".npy"), np.atleast_1d(a))
 
 
 def host_enqueue_leg(workload, batch, bf16):
@@ -692,7 +733,10 @@ def main():
                                       with_points=args.workload != "camera")
     ac = torch.bfloat16 if args.autocast == "bf16" else None
     trainer = train.Trainer(step, device=device, autocast_dtype=ac, channels_last=not args.nchw)
-    dt, loss = timed_steps(trainer, batch, args, world, device)
+    dt, loss, out = timed_steps(trainer, batch, args, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, out, args.dump_outputs)
+    del out
     from unidistill_amd.ops import wgrad_stream
     wgrad_state = wgrad_stream.state()
     if wgrad_state == "ddp":
@@ -707,7 +751,7 @@ def main():
         torch.manual_seed(1234)
         step16 = train.DistillStep(args.workload) if wl["kind"] == "distill" else train.DetectStep(args.workload)
         trainer16 = train.Trainer(step16, device=device, autocast_dtype=torch.bfloat16, channels_last=not args.nchw)
-        dt16, loss16 = timed_steps(trainer16, batch, args, world, device)
+        dt16, loss16, _ = timed_steps(trainer16, batch, args, world, device)
         bf16 = {"value": args.batch * world * args.steps / dt16, "unit": "samples/s",
                 "ms_per_step": dt16 / args.steps * 1e3, "dtype": "bf16", "steps": args.steps, "warmup": args.warmup,
                 "final_loss": loss16, "precision": PRECISION_NOTE[torch.bfloat16],

@@ -15,7 +15,7 @@ def test_two_rank_bench_completes(hip_lib):
     env = dict(os.environ, UD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--workload", "lidar", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--gpus", "2", "--workload", "lidar", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]

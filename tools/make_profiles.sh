@@ -4,15 +4,16 @@
 # bench.py reads for its `traffic` figures.
 #   gpurun --timeout 2400 -- 'bash tools/make_profiles.sh r04'
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 R=${1:-r06}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 T=$GRAFT_REPO_ROOT/tools
 # 1. the bench command itself: kernel trace; summary restricted to the steady state (no warm-up / MIOpen find kernels)
-rm -rf /tmp/p_bench; rocprofv3 --kernel-trace --stats -d /tmp/p_bench -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
+rm -rf /tmp/p_bench; rocprofv3 --kernel-trace --stats -d /tmp/p_bench -- python $REPO/bench.py --full --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
 DB=$(ls -S /tmp/p_bench/*/*.db | head -1)   # the bench process itself: the LARGEST database (bench.py times the host enqueue in a child process, whose trace is a second, smaller file)
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline  ($R)"; echo; echo "The JSON line below was measured UNDER the tracer (about 8 us added per launch, ~2 000 launches per step: ms_per_step is ~15 ms above the un-instrumented run that bench.py / the driver reports); it is kept for the kernel table's context, not as the result."; echo;
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline  ($R)"; echo; echo "The JSON line below was measured UNDER the tracer (about 8 us added per launch, ~2 000 launches per step: ms_per_step is ~15 ms above an un-instrumented bench.py run); it is kept for the kernel table's context, not as the result."; echo;
   echo '```'; grep "^{\"metric\"" $OUT/bench_stdout.txt | cut -c1-3000; echo '```'; echo;
   echo "## Roofline kernels of the bench legs (rocprofv3 durations; bench.py's own HIP-event figures are in the JSON above)"; echo;
   python $T/rocpd_summary.py $DB | grep -E "^\| kernel|^\|---|k_pool<4|k_vp_|k_scan|k_gather|k_bin|k_cell|k_fill|k_conv_f32_taps|k_conv3x3_wino4_f32|k_wino4_fixup|k_wino4_wgrad|k_conv3x3_wino_f32|k_wino_wgrad|k_insert2|k_first_assign|k_gather_clean|k_conv3x3_taps|k_conv_mfma_v2|k_conv_dma_f32|k_conv3x3_wgrad_f32|k_conv1x1_wgrad_f32";
