@@ -10,6 +10,7 @@
 // (((m0 x + m1 y) + m2 z) + m3), no contraction, so the float32 results match numpy's bit for bit.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "image_norm.h"
 
 namespace {
 
@@ -46,21 +47,13 @@ __global__ __launch_bounds__(256) void k_points_transform(const float* __restric
 // the loader ships uint8 pixels (a quarter of the bytes of the reference's float32 tensors).
 // out_cl == 0: out f32 [NI][3][H][W] (the reference's layout); out_cl == 1: [NI][H][W][3] memory (channels-last view).
 __global__ __launch_bounds__(256) void k_image_normalize(const unsigned char* __restrict__ img,
-                                                         float* __restrict__ out, float m0, float m1, float m2,
-                                                         float s0, float s1, float s2, int to_rgb, long long npix_img,
+                                                         float* __restrict__ out, UdNorm nm, long long npix_img,
                                                          long long total, int out_cl) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;      // one pixel of one image
   if (t >= total) return;
   const unsigned char* p = img + t * 3;
-  float v0 = (float)p[0], v1 = (float)p[1], v2 = (float)p[2];
-  if (to_rgb) {
-    const float tmp = v0;
-    v0 = v2;
-    v2 = tmp;
-  }
-  v0 = __fmul_rn(__fsub_rn(v0, m0), s0);
-  v1 = __fmul_rn(__fsub_rn(v1, m1), s1);
-  v2 = __fmul_rn(__fsub_rn(v2, m2), s2);
+  float v0, v1, v2;
+  ud_norm_apply(nm, p[0], p[1], p[2], v0, v1, v2);
   if (out_cl) {
     out[t * 3 + 0] = v0;
     out[t * 3 + 1] = v1;
@@ -111,11 +104,9 @@ extern "C" int ud_image_normalize(const unsigned char* img, float* out, const fl
     if (!(std[c] != 0.0f)) return UD_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   const long long npix = (long long)H * W, total = npix * NI;
-  // mmcv: mean -> float64, stdinv = 1 / float64(std); OpenCV applies both to the float32 image in float32
-  const float s0 = (float)(1.0 / (double)std[0]), s1 = (float)(1.0 / (double)std[1]), s2 = (float)(1.0 / (double)std[2]);
+  const UdNorm nm = ud_norm_make(mean, std, to_rgb);
   UdProfScope prof("input.k_image_normalize", stream);
-  k_image_normalize<<<ud_div_up(total, 256), 256, 0, stream>>>(img, out, mean[0], mean[1], mean[2], s0, s1, s2,
-                                                               to_rgb ? 1 : 0, npix, total, out_channels_last ? 1 : 0);
+  k_image_normalize<<<ud_div_up(total, 256), 256, 0, stream>>>(img, out, nm, npix, total, out_channels_last ? 1 : 0);
   UD_LAUNCH_CHECK();
   return UD_OK;
 }

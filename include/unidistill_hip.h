@@ -671,6 +671,38 @@ int ud_image_normalize(const unsigned char* img, float* out, const float* mean, 
 int ud_collate_pad(const float* const* samples, const int64_t* rows, int B, int64_t L, int W, float* out,
                    ud_stream_t stream);
 
+/* ---- camera augmentation ---------------------------------------------------------------
+ * ImageAffineTransformation.forward (data/multisensorfusion/transforms3d.py:298-347 -> functional.img_transform,
+ * functional.py:560-592): PIL resize (BICUBIC) -> crop (zero fill) -> optional FLIP_LEFT_RIGHT -> rotate (NEAREST,
+ * centre, black fill) of N uint8 RGB frames, bit-exact to Pillow, each frame with its own parameters.  The host
+ * (ops/input_prep.py plan_frames) fills one record per frame, every field int64:
+ *   src_off    byte offset in img of the frame's first stored source row, src_row0 = that row's index,
+ *              src_rows = rows stored (a frame may ship only the row band its crop needs); row_stride bytes apart
+ *   ws_off     byte offset of the frame's horizontal-pass rows in the workspace (16-aligned)
+ *   htab/vtab  device addresses of the int32 resampling tables (W -> rw, H -> rh): rows of (lo, count,
+ *              hk / vk weights in 22-bit fixed point), Pillow's precompute_coeffs + normalize_coeffs_8bpc
+ *   rw, rh     resized size; cx, cy: crop origin in the resized image
+ *   col0/ncols resized columns inside the crop; band0/band_rows: source rows the crop rows' vertical taps touch
+ *   flip       FLIP_LEFT_RIGHT of the crop; rotate: 1 = output (x, y) reads crop pixel ((a2 + a1 y + a0 x) >> 16,
+ *              (a5 + a4 y + a3 x) >> 16) or the fill when outside (Pillow's 16.16 NEAREST affine), 0 = copy
+ * img u8 [.][H][W][3] (device, img_bytes long); out_mode 0: out u8 [N][fH][fW][3]; 1: f32 [N][3][fH][fW] and 2: f32
+ * [N][fH][fW][3], both through ud_image_normalize's arithmetic (mean/std: HOST float[3], ignored for mode 0).
+ * frames_host / frames_dev: the same N records on the host (validated, launch geometry) and on the device.
+ * Workspace: ud_image_affine_workspace_bytes(frames_host, N) bytes (a pure function of the records). */
+typedef struct UdImageAffineFrame {
+  int64_t src_off, src_row0, src_rows, ws_off, htab, vtab, hk, vk, rw, rh, cx, cy;
+  int64_t col0, ncols, band0, band_rows, flip, rotate, a0, a1, a2, a3, a4, a5;
+} UdImageAffineFrame;
+size_t ud_image_affine_workspace_bytes(const UdImageAffineFrame* frames_host, int N);
+/* The launcher's bounds check of the records, as a pure host function: UD_OK, UD_ERR_INVALID_ARG (a band not stored or
+ * outside img_bytes, crop columns outside the resized image, bad sizes) or UD_ERR_WORKSPACE (workspace_bytes too small). */
+int ud_image_affine_check(const UdImageAffineFrame* frames_host, int N, int64_t img_bytes, int H, int W,
+                          int64_t row_stride, int fH, int fW, size_t workspace_bytes);
+int ud_image_affine(const unsigned char* img, int64_t img_bytes, int H, int W, int64_t row_stride,
+                    const UdImageAffineFrame* frames_host, const UdImageAffineFrame* frames_dev, int N, int fH, int fW,
+                    int out_mode, void* out, const float* mean, const float* std, int to_rgb, void* workspace,
+                    size_t workspace_bytes, ud_stream_t stream);
+
 /* ---- frozen ResNet stem (image branch) ----------------------------------------------------------------
  * conv1 (7x7 / stride 2 / pad 3, 3 -> 64, no bias) + bn1 (eval mode, folded to scale / shift) + ReLU, then max-pool 3x3 /
  * stride 2 / pad 1, of the mmdet ResNet-50 the reference builds in unidistill/layers/blocks_3d/mmdet3d/lss_fpn.py:143-149 with
