@@ -11,6 +11,7 @@
 #include "ud_common.h"
 #include "ud_prof.h"
 #include "image_norm.h"
+#include "points_xform.h"
 
 namespace {
 
@@ -25,10 +26,8 @@ __global__ __launch_bounds__(256) void k_points_transform(const float* __restric
   const double* m = mats + (size_t)s * 16;
   const float* src = in + (size_t)(begin + i) * D;
   float* dst = out + (size_t)(begin + i) * D;
-  const double x = src[0], y = src[1], z = src[2];
   float r[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = (float)(((m[4 * k] * x + m[4 * k + 1] * y) + m[4 * k + 2] * z) + m[4 * k + 3]);
+  ud_points_xform(m, src[0], src[1], src[2], r);
   for (int c = 3; c < D; ++c) dst[c] = src[c];          // before xyz: in-place calls read src first
   dst[0] = r[0];
   dst[1] = r[1];

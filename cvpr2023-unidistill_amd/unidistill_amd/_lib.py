@@ -122,6 +122,11 @@ _SIGS = {
     "ud_image_affine_check": (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_i64, c_int, c_int, c_size_t]),
     "ud_image_affine": (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, c_void_p, c_void_p] + [c_int] * 4
                         + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
+    "ud_lidar_prep_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
+    "ud_lidar_prep_count": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
+                            + [c_size_t, c_void_p]),
+    "ud_lidar_prep_compact": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
+                              + [c_i64, c_int, c_void_p, c_i64, c_void_p, c_size_t, c_void_p]),
     "ud_stem_pack_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p]),
     "ud_stem_conv7x7_bn_relu": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_void_p]),
     "ud_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),

@@ -155,7 +155,10 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
     ``ida_aug`` ([sweeps][cams] tuples from ImageAffineTransformation.sample_augs, as its loader-side forward stores
     them): the reference's ImageAffineTransformation + ImageNormalize then run here, in one image_affine launch for
     the batch (only each frame's crop row band travels), and ``mats_dict["ida_mats"]`` is built from the same augs.
-    Samples without ``ida_aug`` draw theirs from ``ida_transform`` (an ImageAffineTransformation), camera by camera."""
+    Samples without ``ida_aug`` draw theirs from ``ida_transform`` (an ImageAffineTransformation), camera by camera.
+    A sample may carry its RAW clouds ``points_raw`` (key frame first, then its sweeps, float32 [Ni, D] arrays) with
+    the ``lidar_aug`` record CollectLidarSweeps / BevAffineTransformation / ObjectRangeFilter leave in the loader:
+    ``points`` is then built by lidar_prep_host_clouds, one H2D copy and one fused pass for the batch."""
     device = torch.device(device)
     batch = {}
     ida_mats = None
@@ -172,6 +175,9 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
         fdim = tuple(ida_transform.aug_conf["final_dim"]) if ida_transform is not None else IMG_DIM
         batch["imgs"], mats = image_affine_host_frames(frames, augs, device, final_dim=fdim)
         ida_mats = torch.from_numpy(mats).to(device=device, dtype=torch.float32)
+    if "points_raw" in data[0]:
+        batch["points"] = lidar_prep_host_clouds([d["points_raw"] for d in data], [d.get("lidar_aug") for d in data],
+                                                 device)
     if "imgs_u8" in data[0]:
         u8 = torch.stack([torch.as_tensor(np.asarray(d["imgs_u8"])) for d in data]).to(device, non_blocking=True)
         batch["imgs"] = image_normalize(u8)
@@ -538,3 +544,345 @@ def image_affine_host_frames(frames, augs, device, final_dim=(256, 704), **kw):
     else:
         out = out.reshape(*lead, fH, fW, 3)
     return out, mats.reshape(*lead, 4, 4)
+
+
+# ---- LiDAR input chain after collate -----------------------------------------------------------
+# The reference's det augmentor runs CollectLidarSweeps -> BevAffineTransformation -> ObjectRangeFilter on every
+# sample's points in the loader (transforms3d.py:379-443, :242-287).  Here the loader-side classes only draw the
+# parameters, do the box-level work (a few dozen boxes) and record in data_dict["lidar_aug"] what the device must do
+# with the points; collate_fn stages the raw clouds of the whole batch in pinned memory, copies them in one H2D copy
+# and runs the per-point work in one fused pass (ud_lidar_prep_count + ud_lidar_prep_compact): sweep transform, BDA,
+# range test, stable compaction and the zero-padded [B, Nmax, D] stack of fill_batch_tensor.
+_SEG_PAR, _SMP_PAR, _MAX_SEG = 18, 24, 64          # include/unidistill_hip.h UD_LIDAR_*
+
+
+def _align16(n):
+    return (n + 15) // 16 * 16
+
+
+def _lidar_tables(seg_rows, sample_nseg, seg_mats, seg_xform, seg_last, bdas, ranges):
+    """Host plan of ud_lidar_prep_*: segment row offsets, per-sample segment offsets and the two parameter tables,
+    packed into one byte buffer (16-byte aligned sections).  -> (bytes, {name: (offset, array)})."""
+    S, B = len(seg_rows), len(sample_nseg)
+    seg = np.zeros(S + 1, np.int64)
+    seg[1:] = np.cumsum(seg_rows)
+    sseg = np.zeros(B + 1, np.int64)
+    sseg[1:] = np.cumsum(sample_nseg)
+    sp = np.zeros((S, _SEG_PAR), np.float64)
+    for s in range(S):
+        if seg_xform[s]:
+            sp[s, :16] = np.asarray(seg_mats[s], np.float64).reshape(16)
+            sp[s, 17] = 1.0
+        sp[s, 16] = seg_last[s]
+    bp = np.zeros((B, _SMP_PAR), np.float64)
+    for b in range(B):
+        if bdas[b] is not None:
+            bp[b, :16] = np.asarray(bdas[b], np.float64).reshape(16)
+            bp[b, 22] = 1.0
+        if ranges[b] is not None:
+            bp[b, 16:22] = np.asarray(ranges[b], np.float32).reshape(6)       # float32 values, exact in float64
+            bp[b, 23] = 1.0
+    parts, off = {}, 0
+    for name, a in (("seg", seg), ("sseg", sseg), ("seg_par", sp), ("smp_par", bp)):
+        parts[name] = (off, a)
+        off = _align16(off + a.nbytes)
+    buf = np.zeros(off, np.uint8)
+    for o, a in parts.values():
+        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    return buf, parts
+
+
+def _lidar_run(pts_ptr, rows, D, parts, plan_base, device, stream, out_compact):
+    """ud_lidar_prep_count -> counts read back (waits on ``stream`` only) -> ud_lidar_prep_compact, all on ``stream``
+    (a torch.cuda.Stream, current while this runs).  -> (out, counts int64 numpy)."""
+    lib = _lib.load()
+    seg, sseg = parts["seg"][1], parts["sseg"][1]
+    S, B = len(seg) - 1, len(sseg) - 1
+    p = {k: plan_base + o for k, (o, _) in parts.items()}
+    ws_bytes = int(lib.ud_lidar_prep_workspace_bytes(seg.ctypes.data, sseg.ctypes.data, S, B))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    counts_d = torch.empty(max(B, 1), dtype=torch.int64, device=device)
+    hs = stream.cuda_stream
+    args = (pts_ptr, rows, D, seg.ctypes.data, sseg.ctypes.data, S, B, p["seg"], p["sseg"], p["seg_par"], p["smp_par"])
+    _lib.check(lib.ud_lidar_prep_count(*args, _lib.ptr(counts_d), _lib.ptr(ws), ws_bytes, hs), "ud_lidar_prep_count")
+    counts_h = torch.empty(max(B, 1), dtype=torch.int64, pin_memory=True)
+    counts_h.copy_(counts_d, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    ev.synchronize()                                    # this stream's work only, not the caller's queue
+    counts = counts_h.numpy()[:B].copy()
+    nmax = int(counts.max()) if B else 0
+    if out_compact:
+        out = torch.empty((int(counts.sum()), D), dtype=torch.float32, device=device)
+    else:
+        out = torch.empty((B, nmax, D), dtype=torch.float32, device=device)
+    out_rows = out.numel() // D
+    _lib.check(lib.ud_lidar_prep_compact(*args, counts.ctypes.data, _lib.ptr(counts_d), nmax, 1 if out_compact else 0,
+                                         _lib.ptr(out), out_rows, _lib.ptr(ws), ws_bytes, hs), "ud_lidar_prep_compact")
+    return out, counts
+
+
+def points_range_filter(points, point_cloud_range, seg=None):
+    """ObjectRangeFilter.mask_points_by_range + indexing (transforms3d.py:248-255) for a device cloud points f32
+    [rows, D]: keeps x in [r0, r3] and y in [r1, r4] (float32 compares, z untested, NaN dropped), in order.  ``seg``:
+    row offsets of segments (S + 1 ints) filtered each on its own, e.g. the samples of a concatenated batch.
+    -> (kept rows f32 [K, D], per-segment kept counts int64 numpy [S]).  Runs on the current stream."""
+    _lib.require_gpu(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous():
+        raise ValueError("points must be a contiguous float32 [rows, D >= 3] tensor")
+    rows, D = points.shape
+    seg = [0, rows] if seg is None else [int(v) for v in seg]
+    if len(seg) < 1 or seg[0] != 0 or seg[-1] != rows or any(b < a for a, b in zip(seg, seg[1:])):
+        raise ValueError("seg must ascend from 0 to the number of rows")
+    S = len(seg) - 1
+    rng = np.asarray(point_cloud_range, np.float32).reshape(6)
+    buf, parts = _lidar_tables(np.diff(seg), [1] * S, [None] * S, [False] * S, [np.nan] * S, [None] * S, [rng] * S)
+    device = points.device
+    plan = torch.from_numpy(buf).to(device)
+    stream = torch.cuda.current_stream(device)
+    return _lidar_run(_lib.ptr(points), rows, D, parts, plan.data_ptr(), device, stream, True)
+
+
+def sweep_time_lag(info, sweep):
+    """The value CollectLidarSweeps writes into a sweep's last column (D == 5): float64 seconds, stored as float32."""
+    return np.float32((info["timestamp"] - sweep["sweep_lidar_timestamp"]) / 1e6)
+
+
+def _lidar_aug(data_dict):
+    """data_dict["lidar_aug"], created for a lone key frame when no CollectLidarSweeps ran before."""
+    a = data_dict.get("lidar_aug")
+    if a is None:
+        a = data_dict["lidar_aug"] = {"segments": [len(data_dict["points"])], "sweep_mats": np.zeros((0, 4, 4)),
+                                      "time_lags": np.zeros(0, np.float32), "bda_mat": None, "range": None}
+    return a
+
+
+class CollectLidarSweeps:
+    """CollectLidarSweeps (transforms3d.py:379-414) split for the device: in the loader it records the sweep -> key
+    matrices (sweep_to_key_matrix, float64) and the time lags in data_dict["lidar_aug"] and pops
+    info["sweep_lidar_infos"] as the reference does; ``points`` and ``sweep_points`` stay raw.  The sample's
+    ``points_raw`` = [points] + sweep_points then goes to collate_fn with the record."""
+
+    def forward(self, data_dict):
+        if data_dict.get("points", None) is not None:
+            info = data_dict["info"]
+            sweeps = list(data_dict.get("sweep_points", []))
+            infos = info["sweep_lidar_infos"][:len(sweeps)]
+            mats = [sweep_to_key_matrix(info["lidar_to_ego"], info["ego_to_global"], s["sweep_lidar_to_ego"])
+                    for s in infos]
+            data_dict["lidar_aug"] = {
+                "segments": [len(data_dict["points"])] + [len(s) for s in sweeps],
+                "sweep_mats": np.stack(mats) if mats else np.zeros((0, 4, 4)),
+                "time_lags": np.array([sweep_time_lag(info, s) for s in infos], np.float32),
+                "bda_mat": None, "range": None}
+            info.pop("sweep_lidar_infos")
+        return data_dict
+
+    def __call__(self, data_dict):
+        return self.forward(data_dict)
+
+
+def bda_boxes(gt_boxes, mat, rotate_deg, scale, flip_dx, flip_dy):
+    """functional.bev_transform's box arithmetic (functional.py:633-646) on host boxes float32 [M, 7 | 9], in the
+    reference's precisions: centres through the float64 matrix, sizes * scale and yaw in float32 (numpy's rules for
+    a Python-float operand), velocities through mat[:2, :2] in float64.  Returns a new array."""
+    boxes = np.array(gt_boxes, copy=True)
+    if boxes.shape[0] == 0:
+        return boxes
+    hc = np.ones((boxes.shape[0], 4))
+    hc[:, :3] = boxes[:, :3]
+    boxes[:, :3] = (mat @ hc.T).T[:, :3]
+    boxes[:, 3:6] *= scale
+    boxes[:, 6] += rotate_deg / 180 * np.pi
+    if flip_dx:
+        boxes[:, 6] = np.pi - boxes[:, 6]
+    if flip_dy:
+        boxes[:, 6] = -boxes[:, 6]
+    if boxes.shape[1] > 7:
+        boxes[:, 7:] = (mat[:2, :2] @ boxes[:, 7:].T).T
+    return boxes
+
+
+class BevAffineTransformation:
+    """BevAffineTransformation (transforms3d.py:417-443) split for the device.  ``sample_augs`` draws from np.random
+    in the reference's order; ``forward`` transforms gt_boxes on the host (bda_boxes), stores data_dict["bda_mat"]
+    when ``imgs`` is present (the camera branch reads it) and records the matrix for the points in
+    data_dict["lidar_aug"]; the points themselves are transformed on the device after collate."""
+
+    def __init__(self, **bda_aug_conf):
+        self.aug_conf = bda_aug_conf
+
+    def sample_augs(self):
+        c = self.aug_conf
+        rotate = np.random.uniform(*c["rot_lim"])
+        scale = np.random.uniform(*c["scale_lim"])
+        trans = np.random.normal(scale=c["trans_lim"])
+        flip_dx = np.random.uniform() < c["flip_dx_ratio"]
+        flip_dy = np.random.uniform() < c["flip_dy_ratio"]
+        return rotate, scale, trans, flip_dx, flip_dy
+
+    def forward(self, data_dict):
+        rotate, scale, trans, flip_dx, flip_dy = self.sample_augs()
+        mat = bev_transform_matrix(rotate, scale, trans, flip_dx, flip_dy)
+        data_dict["gt_boxes"] = bda_boxes(data_dict["gt_boxes"], mat, rotate, scale, flip_dx, flip_dy)
+        if data_dict.get("points", None) is not None:
+            a = _lidar_aug(data_dict)
+            if a["bda_mat"] is not None or a["range"] is not None:
+                raise ValueError("BevAffineTransformation must come once, before ObjectRangeFilter")
+            a["bda_mat"] = mat
+        if data_dict.get("imgs", None) is not None:
+            data_dict["bda_mat"] = mat
+        return data_dict
+
+    def __call__(self, data_dict):
+        return self.forward(data_dict)
+
+
+_CORNERS = np.array([[0, 0, 0], [0, 0, 1], [0, 1, 1], [0, 1, 0], [1, 0, 0], [1, 0, 1], [1, 1, 1], [1, 1, 0]])
+
+
+def boxes_in_range_mask(gt_boxes, point_cloud_range, min_num_corners=1):
+    """ObjectRangeFilter's box test (transforms3d.py:258-271): a box stays when at least ``min_num_corners`` of its 8
+    corners (origin (0.5, 0.5, 0.5), yaw about z) lie inside the range, bounds included.  float32 throughout, the
+    rotation as the same einsum contraction the reference evaluates, so boundary corners decide alike."""
+    b = np.asarray(gt_boxes)[:, :7]
+    r = np.asarray(point_cloud_range, np.float32)
+    dims = b[:, 3:6]
+    unit = _CORNERS.astype(dims.dtype) - np.array((0.5, 0.5, 0.5), dtype=dims.dtype)
+    local = dims.reshape(-1, 1, 3) * unit.reshape(1, 8, 3)
+    c, s = np.cos(b[:, 6]), np.sin(b[:, 6])
+    zero, one = np.zeros_like(c), np.ones_like(c)
+    rot_t = np.stack([[c, s, zero], [-s, c, zero], [zero, zero, one]])            # [3, 3, M]: row-vector rotation
+    corners = np.einsum("aij,jka->aik", local, rot_t)
+    corners += b[:, :3].reshape(-1, 1, 3)
+    inside = ((corners >= r[:3]) & (corners <= r[3:])).all(axis=2)
+    return inside.sum(axis=1) >= min_num_corners
+
+
+class ObjectRangeFilter:
+    """ObjectRangeFilter (transforms3d.py:242-287) split for the device: records the range for the points in
+    data_dict["lidar_aug"] (applied after collate, after the BDA) and filters gt_boxes / gt_names / gt_labels on the
+    host, so the dataset's filter_empty redraw sees the filtered box count.  The reference's ``self.training`` is
+    always True (Compose keeps its transforms in a plain list, train() never reaches them)."""
+
+    def __init__(self, point_cloud_range):
+        self.point_cloud_range = np.array(point_cloud_range, dtype=np.float32)
+
+    def forward(self, data_dict):
+        if data_dict.get("points", None) is not None:
+            _lidar_aug(data_dict)["range"] = self.point_cloud_range.copy()
+        if len(data_dict.get("gt_boxes", [])) > 0:
+            mask = boxes_in_range_mask(data_dict["gt_boxes"], self.point_cloud_range)
+            data_dict["gt_boxes"] = data_dict["gt_boxes"][mask]
+            for k in ("gt_names", "gt_labels"):
+                if data_dict.get(k, None) is not None:
+                    data_dict[k] = data_dict[k][mask]
+        return data_dict
+
+    def __call__(self, data_dict):
+        return self.forward(data_dict)
+
+
+_input_streams = {}       # device index -> torch.cuda.Stream for the input chain
+_lidar_staging = {}       # device index -> [pinned uint8 buffer, event after its last H2D copy]
+
+
+def _device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def input_stream(device):
+    """The per-device stream the LiDAR input chain runs on: its H2D copy and passes never queue behind the training
+    step on the caller's stream, so the count readback waits for them alone."""
+    i = _device_index(device)
+    s = _input_streams.get(i)
+    if s is None:
+        s = _input_streams[i] = torch.cuda.Stream(device=torch.device("cuda", i))
+    return s
+
+
+def _staging(i, nbytes):
+    st = _lidar_staging.get(i)
+    if st is None or st[0].numel() < nbytes:
+        if st is not None:
+            st[1].synchronize()
+        st = _lidar_staging[i] = [torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True),
+                                  torch.cuda.Event()]
+        st[1].record(torch.cuda.current_stream(torch.device("cuda", i)))
+    else:
+        st[1].synchronize()                 # the previous batch's copy out of this buffer has finished
+    return st
+
+
+def _plan_segments(clouds, aug, D):
+    """Per segment (matrix, transform?, last-column value) and the sample's (BDA, range) from its lidar_aug record."""
+    n = len(clouds)
+    if aug is None:                         # rows copied as they are
+        return [None] * n, [False] * n, [np.nan] * n, None, None
+    segs = [int(v) for v in aug["segments"]]
+    if segs != [len(c) for c in clouds]:
+        raise ValueError(f"lidar_aug segments {segs} do not match the clouds' rows {[len(c) for c in clouds]}")
+    mats = np.asarray(aug["sweep_mats"], np.float64).reshape(-1, 4, 4)
+    lags = np.asarray(aug["time_lags"], np.float32).reshape(-1)
+    if len(mats) != n - 1 or len(lags) != n - 1:
+        raise ValueError("lidar_aug needs one sweep matrix and one time lag per sweep")
+    last = [0.0] + [float(v) for v in lags] if D == 5 else [np.nan] * n
+    return [None] + list(mats), [False] + [True] * (n - 1), last, aug.get("bda_mat"), aug.get("range")
+
+
+def lidar_prep_host_clouds(clouds, plans, device):
+    """The reference's CollectLidarSweeps -> BevAffineTransformation -> ObjectRangeFilter on the points, then
+    collate_fn's fill_batch_tensor, for host clouds: ``clouds`` one list per sample of float32 [Ni, D] arrays (key
+    frame first, then its sweeps), ``plans`` the samples' data_dict["lidar_aug"] records (None: rows taken as they
+    are).  All clouds are packed into a pinned buffer, copied in one H2D copy and processed in one fused pass on
+    input_stream(device); the caller's current stream waits on the result.  -> float32 [B, Nmax, D] on ``device``,
+    equal to fill_batch_tensor of the reference-processed clouds bit for bit."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+    if len(clouds) != len(plans) or not clouds:
+        raise ValueError("one plan per sample, at least one sample")
+    arrs = [[np.asarray(c.numpy() if torch.is_tensor(c) else c) for c in cs] for cs in clouds]
+    flat = [a for cs in arrs for a in cs]
+    if not flat or any(a.dtype != np.float32 or a.ndim != 2 for a in flat):
+        raise ValueError("clouds must be float32 [N, D] arrays")
+    D = flat[0].shape[1]
+    if D < 3 or any(a.shape[1] != D for a in flat):
+        raise ValueError("clouds must share one D >= 3")
+    if any(len(cs) == 0 or len(cs) > _MAX_SEG for cs in arrs):
+        raise ValueError(f"every sample needs 1 .. {_MAX_SEG} clouds")
+    seg_rows, nseg, mats, xform, last, bdas, ranges = [], [], [], [], [], [], []
+    for cs, aug in zip(arrs, plans):
+        m, x, l, bda, rg = _plan_segments(cs, aug, D)
+        seg_rows += [len(a) for a in cs]
+        nseg.append(len(cs))
+        mats += m
+        xform += x
+        last += l
+        bdas.append(bda)
+        ranges.append(rg)
+    plan, parts = _lidar_tables(seg_rows, nseg, mats, xform, last, bdas, ranges)
+    rows = int(sum(seg_rows))
+    pts_bytes = _align16(rows * D * 4)
+    i = _device_index(device)
+    device = torch.device("cuda", i)
+    host, copied = _staging(i, pts_bytes + plan.nbytes)
+    hv = host.numpy()
+    fv = hv[:rows * D * 4].view(np.float32)
+    off = 0
+    for a in flat:
+        fv[off:off + a.size] = a.reshape(-1)
+        off += a.size
+    hv[pts_bytes:pts_bytes + plan.nbytes] = plan
+    cur = torch.cuda.current_stream(device)
+    s = input_stream(device)
+    with torch.cuda.stream(s):
+        dev = torch.empty(pts_bytes + plan.nbytes, dtype=torch.uint8, device=device)
+        dev.copy_(host[:dev.numel()], non_blocking=True)
+        copied.record(s)
+        out, _ = _lidar_run(dev.data_ptr(), rows, D, parts, dev.data_ptr() + pts_bytes, device, s, False)
+        done = torch.cuda.Event()
+        done.record(s)
+    cur.wait_event(done)
+    out.record_stream(cur)
+    return out

@@ -703,6 +703,39 @@ int ud_image_affine(const unsigned char* img, int64_t img_bytes, int H, int W, i
                     int out_mode, void* out, const float* mean, const float* std, int to_rgb, void* workspace,
                     size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- LiDAR input chain after collate -------------------------------------------------------
+ * CollectLidarSweeps -> BevAffineTransformation -> ObjectRangeFilter (data/multisensorfusion/transforms3d.py:379-443,
+ * :242-287) on the points, then collate_fn's zero-padded stack (nuscenes_multimodal.py:441-463), for a whole batch.
+ * pts f32 [rows][D] (device): S segments, segment s = rows seg[s] .. seg[s+1]; sample b = segments
+ * sample_seg[b] .. sample_seg[b+1] (key frame first, then its sweeps; at most UD_LIDAR_MAX_SEGMENTS).  seg / sample_seg
+ * are given on the host (validation, launch geometry) and on the device.  Per row:
+ *   xyz = the segment's matrix applied in float64, rounded to float32 (seg_par[s][17] != 0), else copied;
+ *   then the sample's BDA matrix applied the same way to that float32 result (smp_par[b][22] != 0);
+ *   column D-1 <- seg_par[s][16] when D > 3 and that value is not NaN (time lag; 0 for the key frame when D == 5);
+ *   kept when x >= r0 && x <= r3 && y >= r1 && y <= r4 in float32 (smp_par[b][23] != 0; NaN fails), else always.
+ * Kept rows keep their order.  seg_par f64 [S][UD_LIDAR_SEG_PAR] = matrix (16, row major), last, transform flag;
+ * smp_par f64 [B][UD_LIDAR_SMP_PAR] = BDA matrix (16), range (6 float32 values), has_bda, has_range (device).
+ *   ud_lidar_prep_count   : counts (device int64[B]) <- kept rows per sample
+ *   ud_lidar_prep_compact : with counts_host = those counts read back; compact == 0: out f32 [B][nmax][D], rows
+ *                           counts[b] .. nmax zero (nmax >= every count, out_rows >= B * nmax); compact == 1: the
+ *                           samples' kept rows back to back (out_rows >= their sum).  Same plan as the count call.
+ * Both validate the plan on the host first (UD_ERR_INVALID_ARG: offsets not ascending, D < 3, a NULL pointer with a
+ * non-zero size, too many segments in a sample, B > 65535) and launch nothing when it fails.
+ * Workspace: ud_lidar_prep_workspace_bytes(seg_host, sample_seg_host, S, B), the same buffer for both calls. */
+#define UD_LIDAR_MAX_SEGMENTS 64
+#define UD_LIDAR_SEG_PAR 18
+#define UD_LIDAR_SMP_PAR 24
+size_t ud_lidar_prep_workspace_bytes(const int64_t* seg_host, const int64_t* sample_seg_host, int S, int B);
+int ud_lidar_prep_count(const float* pts, int64_t rows, int D, const int64_t* seg_host, const int64_t* sample_seg_host,
+                        int S, int B, const int64_t* seg_dev, const int64_t* sample_seg_dev, const double* seg_par,
+                        const double* smp_par, int64_t* counts, void* workspace, size_t workspace_bytes,
+                        ud_stream_t stream);
+int ud_lidar_prep_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                          const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                          const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                          const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact, float* out,
+                          int64_t out_rows, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+
 /* ---- frozen ResNet stem (image branch) ----------------------------------------------------------------
  * conv1 (7x7 / stride 2 / pad 3, 3 -> 64, no bias) + bn1 (eval mode, folded to scale / shift) + ReLU, then max-pool 3x3 /
  * stride 2 / pad 1, of the mmdet ResNet-50 the reference builds in unidistill/layers/blocks_3d/mmdet3d/lss_fpn.py:143-149 with
