@@ -183,6 +183,8 @@ class _BnActFn(torch.autograd.Function):
         training, relu, has_res = ctx.cfg
         if not training:
             raise NotImplementedError("fused BatchNorm backward covers training-mode statistics only")
+        if y is not None and y.stride() != x.stride():
+            y = _like(y, x)               # written into a channel slice (out=): the backward kernels read the mask source at p * C + c
         lib = _lib.load()
         C = x.shape[1]
         P = x.numel() // C
@@ -252,6 +254,9 @@ def cat_slices(buf, parts):
 def bn_act(bn, x, residual=None, relu=True, out=None):
     """relu(bn(x) + residual) with nn.BatchNorm2d ``bn``'s parameters, buffers and train/eval mode; out: see cat_buffer."""
     tracked = None
+    if bn.training and x.numel() == x.shape[1]:
+        # torch.nn.functional.batch_norm's check: batch statistics of one value per channel are undefined
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
     if bn.training:
         nbt = bn.num_batches_tracked
         if nbt.is_cuda and nbt.dtype == torch.int64 and bn.running_mean.dtype == torch.float32:
