@@ -127,6 +127,10 @@ _SIGS = {
                             + [c_size_t, c_void_p]),
     "ud_lidar_prep_compact": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
                               + [c_i64, c_int, c_void_p, c_i64, c_void_p, c_size_t, c_void_p]),
+    "ud_jpeg_parse": (c_int, [c_void_p, c_i64, c_void_p]),
+    "ud_jpeg_plan": (c_size_t, [c_void_p, c_int]),
+    "ud_jpeg_decode": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
     "ud_stem_pack_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p]),
     "ud_stem_conv7x7_bn_relu": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_void_p]),
     "ud_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),

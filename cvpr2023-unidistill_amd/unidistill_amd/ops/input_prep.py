@@ -11,6 +11,7 @@ import torch
 
 from .. import _lib
 from ..config import IMG_DIM
+from .jpeg import JpegFrameError, jpeg_decode
 
 
 def points_transform(points, seg, mats, last=None, out=None):
@@ -158,7 +159,10 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
     Samples without ``ida_aug`` draw theirs from ``ida_transform`` (an ImageAffineTransformation), camera by camera.
     A sample may carry its RAW clouds ``points_raw`` (key frame first, then its sweeps, float32 [Ni, D] arrays) with
     the ``lidar_aug`` record CollectLidarSweeps / BevAffineTransformation / ObjectRangeFilter leave in the loader:
-    ``points`` is then built by lidar_prep_host_clouds, one H2D copy and one fused pass for the batch."""
+    ``points`` is then built by lidar_prep_host_clouds, one H2D copy and one fused pass for the batch.
+    A sample may carry its camera frames as JPEG files ``imgs_jpeg`` ([sweeps][cams] of bytes, nested like imgs_raw)
+    with ``ida_aug`` (or an ida_transform): they are decoded on the device (ops/jpeg.py, bit-exact to Pillow) and go
+    through the same image_affine launch; a frame whose decode failed raises ValueError naming sample and camera."""
     device = torch.device(device)
     batch = {}
     ida_mats = None
@@ -175,6 +179,8 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
         fdim = tuple(ida_transform.aug_conf["final_dim"]) if ida_transform is not None else IMG_DIM
         batch["imgs"], mats = image_affine_host_frames(frames, augs, device, final_dim=fdim)
         ida_mats = torch.from_numpy(mats).to(device=device, dtype=torch.float32)
+    if "imgs_jpeg" in data[0]:
+        batch["imgs"], ida_mats = _collate_jpeg(data, device, ida_transform)
     if "points_raw" in data[0]:
         batch["points"] = lidar_prep_host_clouds([d["points_raw"] for d in data], [d.get("lidar_aug") for d in data],
                                                  device)
@@ -195,6 +201,50 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
         batch.setdefault("mats_dict", {})["ida_mats"] = ida_mats
     batch["img_metas"] = [d.get("img_metas") for d in data]
     return batch
+
+
+def _collate_jpeg(data, device, ida_transform):
+    """imgs_jpeg route of collate_fn: one jpeg_decode for the batch, the status read back once on the input stream,
+    then image_affine on the decoded frames.  -> (imgs, ida_mats)."""
+    nest, files, augs = None, [], []
+    for b, d in enumerate(data):
+        sweeps = d["imgs_jpeg"]
+        shape = (len(sweeps), len(sweeps[0]) if len(sweeps) else 0)
+        if nest is None:
+            nest = shape
+        if shape != nest or any(len(cams) != shape[1] for cams in sweeps) or not shape[0] or not shape[1]:
+            raise ValueError("imgs_jpeg must be [sweeps][cams] of JPEG bytes, the same nesting in every sample")
+        files += [f for cams in sweeps for f in cams]
+        a = d.get("ida_aug")
+        if a is None:
+            if ida_transform is None:
+                raise ValueError("imgs_jpeg needs ida_aug per sample or an ida_transform to draw it")
+            a = [ida_transform.sample_augs() for _ in range(shape[0] * shape[1])]
+        a = _flat_augs(a)
+        if len(a) != shape[0] * shape[1]:
+            raise ValueError(f"sample {b}: {len(a)} augs for {shape[0] * shape[1]} frames")
+        augs += a
+    device = torch.device(device)
+    per = nest[0] * nest[1]
+    name = lambda i: f"sample {i // per} sweep {i % per // nest[1]} camera {i % nest[1]}"
+    try:
+        frames, status = jpeg_decode(files, device)
+    except JpegFrameError as e:
+        raise ValueError(f"JPEG decode failed for {name(e.index)}: {e.reason}") from e
+    s = input_stream(device)
+    with torch.cuda.stream(s):       # the readback queues behind the decode only, not the training step
+        st = status.to("cpu", non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(s)
+    ev.synchronize()
+    bad = np.nonzero(st.numpy())[0]
+    if len(bad):
+        where = ", ".join(f"{name(i)} (status {int(st[i])})" for i in bad)
+        raise ValueError(f"JPEG decode failed for {where}")
+    fdim = tuple(ida_transform.aug_conf["final_dim"]) if ida_transform is not None else IMG_DIM
+    H, W = frames.shape[1:3]
+    imgs, mats = image_affine(frames.view(len(data), nest[0], nest[1], H, W, 3), augs, final_dim=fdim)
+    return imgs, torch.from_numpy(mats).to(device=device, dtype=torch.float32)
 
 
 # ---- camera augmentation: ImageAffineTransformation on the device (DESIGN §2.9) -------------------------------
@@ -328,9 +378,14 @@ class ImageAffineTransformation:
         return resize, (newW, newH), (crop_w, crop_h, crop_w + fW, crop_h + fH), flip, rotate
 
     def forward(self, data_dict):
-        if data_dict.get("imgs", None) is not None:
+        """Draws per camera of data_dict["imgs"] (frames or their JPEG bytes: the values are not read), or of
+        data_dict["imgs_jpeg"] when there is no "imgs"."""
+        imgs = data_dict.get("imgs", None)
+        if imgs is None:
+            imgs = data_dict.get("imgs_jpeg", None)
+        if imgs is not None:
             data_dict["ida_aug"], data_dict["ida_mat"] = {}, {}
-            for cam in data_dict["imgs"].keys():
+            for cam in imgs.keys():
                 augs = self.sample_augs()
                 data_dict["ida_aug"][cam] = augs
                 data_dict["ida_mat"][cam] = ida_matrix(augs[0], augs[2], augs[3], augs[4])

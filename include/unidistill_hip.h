@@ -736,6 +736,57 @@ int ud_lidar_prep_compact(const float* pts, int64_t rows, int D, const int64_t* 
                           const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact, float* out,
                           int64_t out_rows, void* workspace, size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- JPEG decode after collate -------------------------------------------------------------
+ * The reference reads every camera frame with skimage_io.imread (nuscenes_multimodal.py:171-177, :197), i.e. Pillow's
+ * libjpeg-turbo.  Baseline / extended-sequential Huffman JPEGs (SOF0 / SOF1), 8-bit, three components YCbCr in one
+ * interleaved scan, luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, with or without restart intervals, decode here bit for
+ * bit as Pillow decodes them: ISLOW IDCT, fancy upsampling, jdcolor's fixed-point YCbCr -> RGB.
+ *   ud_jpeg_parse  : HOST only.  Reads the markers of one file into a record (geometry, quantisation tables in natural
+ *                    order, per component the DC / AC Huffman lookups, the entropy-coded segment's byte range).
+ *                    UD_JPEG_OK, or UD_JPEG_UNSUPPORTED (progressive, lossless, arithmetic, 12-bit, grayscale, CMYK,
+ *                    RGB, 4:4:0 or other sampling, multi-scan), UD_JPEG_TRUNCATED (the file ends early, no EOI) or
+ *                    UD_JPEG_CORRUPT (inconsistent headers, oversubscribed Huffman tables); nothing is launched for
+ *                    such a file.  The scan's bytes are taken to the end of the data: the decode ends the scan at its
+ *                    first marker other than RSTn (normally EOI; bytes after it are ignored).
+ *   ud_jpeg_plan   : HOST only.  With src_off set by the caller (the file's offset in the packed input), fills each
+ *                    record's out_off (frames back to back, uint8 [H][W][3] each) and workspace offsets; returns the
+ *                    workspace bytes ud_jpeg_decode needs (0 when a record is not a parsed one).
+ *   ud_jpeg_decode : N frames, any mix of sizes and sampling modes, in four launches: destuff + split at RSTn,
+ *                    self-synchronising parallel Huffman decode (UD_JPEG_SUB_BITS-bit subsequences), dequantise + IDCT
+ *                    into component planes, upsample + colour convert into out.  status int32[N] (device) <- 0 or
+ *                    UD_JPEG_ST_* bits; a failed frame's pixels are zeros and the other frames are unaffected.  iters
+ *                    int32[N] (device, may be NULL) <- the synchronisation rounds the Huffman decode needed.
+ * Every bitstream read is clamped to the frame's own entropy-coded bytes; the host checks the records (geometry
+ * consistent with the sizes, regions inside src / out / workspace) before anything is launched. */
+#define UD_JPEG_OK 0
+#define UD_JPEG_UNSUPPORTED 1
+#define UD_JPEG_TRUNCATED 2
+#define UD_JPEG_CORRUPT 3
+#define UD_JPEG_LOOKAHEAD 9
+#define UD_JPEG_SUB_BITS 1024
+#define UD_JPEG_ST_MARKER 1 /* restart numbers out of order or miscounted (the scan ends at its first other marker) */
+#define UD_JPEG_ST_CODE 2   /* an invalid Huffman code or a coefficient index past 63 */
+#define UD_JPEG_ST_LENGTH 4 /* a segment holds fewer or more bytes than its MCUs need */
+typedef struct UdJpegHuff {
+  uint16_t look[1 << UD_JPEG_LOOKAHEAD]; /* code length << 8 | symbol for codes of <= LOOKAHEAD bits, else 0 */
+  int32_t maxcode[18];                   /* largest code of each length, -1 when none */
+  int32_t valoff[18];                    /* index of a length's first symbol minus its first code */
+  uint8_t vals[256];
+} UdJpegHuff;
+typedef struct UdJpegFrame {
+  int32_t width, height, hmax, vmax, mcus_x, mcus_y, bpm, restart, nseg, reserved0;
+  int32_t comp_id[3], h[3], v[3], cw[3], ch[3], reserved1;
+  int64_t ecs_off, ecs_bytes;                           /* entropy-coded segment, relative to the file's first byte */
+  int64_t src_off, out_off, ws_ecs, ws_seg, ws_sub, ws_state, ws_scan, ws_coef, ws_plane[3], nsub_max, total_blocks;
+  uint16_t qt[3][64];                                   /* per component, natural order */
+  UdJpegHuff huff[6];                                   /* component c: [2c] DC, [2c + 1] AC */
+} UdJpegFrame;
+int ud_jpeg_parse(const unsigned char* bytes, int64_t nbytes, UdJpegFrame* out);
+size_t ud_jpeg_plan(UdJpegFrame* frames, int N);
+int ud_jpeg_decode(const unsigned char* src, int64_t src_bytes, const UdJpegFrame* frames_host,
+                   const UdJpegFrame* frames_dev, int N, unsigned char* out, int64_t out_bytes, int32_t* status,
+                   int32_t* iters, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+
 /* ---- frozen ResNet stem (image branch) ----------------------------------------------------------------
  * conv1 (7x7 / stride 2 / pad 3, 3 -> 64, no bias) + bn1 (eval mode, folded to scale / shift) + ReLU, then max-pool 3x3 /
  * stride 2 / pad 1, of the mmdet ResNet-50 the reference builds in unidistill/layers/blocks_3d/mmdet3d/lss_fpn.py:143-149 with
