@@ -131,6 +131,10 @@ _SIGS = {
     "ud_jpeg_plan": (c_size_t, [c_void_p, c_int]),
     "ud_jpeg_decode": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),
+    "ud_nus_pred_to_global": (c_int, [c_void_p, c_i64, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_int]
+                              + [c_void_p] * 7),
+    "ud_nus_eval_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "ud_nus_eval": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_size_t, c_void_p]),
     "ud_stem_pack_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p]),
     "ud_stem_conv7x7_bn_relu": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_void_p]),
     "ud_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),

@@ -331,6 +331,30 @@ class DetectStep(nn.Module):
         return {"loss": ret["loss"].mean(), "tb": tb}
 
 
+class ValidationStep(nn.Module):
+    """validation_step of the base experiments (BEVFusion_nuscenes_base_exp.py): the eval forward under no_grad, then
+    the predictions go to a NuScenesDetectionEval on the device (labels start at 1 there; the evaluator subtracts 1)."""
+
+    def __init__(self, model, evaluator):
+        super().__init__()
+        self.model = model
+        self.evaluator = evaluator
+
+    def forward(self, batch, sample_ids, lidar_to_global):
+        points = batch.get("points")
+        if points is not None and not isinstance(points, (list, tuple)):
+            points = [p for p in points]
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None)
+        finally:
+            self.model.train(was_training)
+        self.evaluator.add_batch(sample_ids, out["pred_dicts"], lidar_to_global)
+        return out["pred_dicts"]
+
+
 def synthetic_batch(device, batch_size=1, rank=0, ncam=6, sweeps=1, n_boxes=40, max_boxes=50,
                     with_points=True, with_imgs=True, seed=1234):
     """collate_fn-shaped synthetic batch on the device."""

@@ -945,6 +945,78 @@ int ud_assign_targets(const float* gt, int B, int M, int cols, const signed char
                       float* hm, long long* ind, unsigned char* mask, long long* cat, float* enc,
                       ud_stream_t stream);
 
+/* ---- nuScenes detection metric, detection_cvpr_2019 ------------------------------------------
+ * The reference's validation_epoch_end -> NuscenesMultiModalData.evaluation (nuscenes_multimodal.py:336-393,
+ * eval_utils.py) ends in the nuScenes devkit's DetectionEval; tests/nus_eval_reference.py restates it in numpy.
+ *   ud_nus_pred_to_global : per prediction row (boxes f32 [n][ncol], ncol 7 or 9 = x y z dx dy dz rot [vx vy], scores
+ *                   f32 [n], labels int64 [n] starting at 1) of a batch whose sample b owns rows batch_off[b] ..
+ *                   batch_off[b+1] (int32, device): the global-frame record rec f64 [n][UD_NUS_PRED_COLS] =
+ *                   x y z w l h yaw vx vy score through the sample's LiDAR->global matrix l2g f64 [B][4][4] (row
+ *                   major), cls int32 = label - 1 and attr int32 (eval_utils' rule from the per-class tables
+ *                   attr_moving / attr_still, -1 = '').  A label outside 1 .. num_classes sets UD_NUS_ST_CLASS in
+ *                   *status (device, OR-ed) and gives cls -1.
+ *   ud_nus_eval   : the metric's curves.  One workgroup per sample: the class-range / num_pts / keep filters, the
+ *                   sample's kept predictions in (class, descending score, descending box) order, greedy matching at
+ *                   the four thresholds (TP flags, matched GT, the five TP errors at dist_th_tp); a stable radix sort
+ *                   of (class, descending score) over the predictions laid out in (sample, box) order and reversed;
+ *                   per (class, threshold) the integer TP cumsum, per (class, error) the NaN-aware cummean over the
+ *                   matches; numpy.interp of precision, confidence and the errors onto the recall points.
+ * Host-checked (UD_ERR_INVALID_ARG, nothing launched): sizes, NULL pointers, num_classes, dist_th_tp_index.  Device
+ * checks set status bits: UD_NUS_ST_CLASS, UD_NUS_ST_SIZE (a matched pair with a size <= 0), UD_NUS_ST_COUNT (more
+ * than UD_NUS_MAX_BOXES boxes of one sample).  Workspace: ud_nus_eval_workspace_bytes(P, num_classes). */
+#define UD_NUS_MAX_CLASSES 15
+#define UD_NUS_PRED_COLS 10
+#define UD_NUS_GT_COLS 9
+#define UD_NUS_MAX_BOXES 1024 /* predictions, and ground-truth boxes, of one sample */
+#define UD_NUS_POINTS 101
+#define UD_NUS_ST_CLASS 1
+#define UD_NUS_ST_SIZE 2
+#define UD_NUS_ST_COUNT 4
+
+typedef struct {
+  int num_classes;
+  int dist_th_tp_index;                       /* which of dist_th is dist_th_tp */
+  int pi_period_class;                        /* class whose yaw period is pi (barrier), -1 = none */
+  int pad_;
+  double class_range[UD_NUS_MAX_CLASSES];
+  double dist_th[4];
+  double rec_pts[UD_NUS_POINTS];              /* numpy.linspace(0, 1, 101) */
+} UdNusCfg;
+
+typedef struct {
+  /* predictions: rows of ud_nus_pred_to_global, each sample's rows contiguous, samples in any order */
+  const double* pred_rec;                     /* [rows][UD_NUS_PRED_COLS] */
+  const int32_t* pred_cls;                    /* [rows], -1 = invalid */
+  const int32_t* pred_attr;                   /* [rows] */
+  const int64_t* pred_src;                    /* [S] first row of sample s */
+  const int64_t* pred_off;                    /* [S + 1] sample s = (sample, box) positions pred_off[s] .. pred_off[s+1] */
+  /* ground truth, samples in order: sample s = rows gt_off[s] .. gt_off[s+1] */
+  const double* gt_rec;                       /* [G][UD_NUS_GT_COLS] x y z w l h yaw vx vy */
+  const int32_t* gt_cls;
+  const int32_t* gt_attr;                     /* -1 = '' */
+  const int32_t* gt_num_pts;
+  const uint8_t* gt_keep;                     /* caller's mask (bike racks) */
+  const int64_t* gt_off;
+  const double* ego;                          /* [S][3] ego translation, global frame */
+  /* outputs */
+  double* prec;                               /* [C][4][101] */
+  double* conf;                               /* [C][4][101] */
+  double* tp_err;                             /* [C][5][101] trans scale orient vel attr */
+  uint8_t* tp;                                /* [4][P] per (sample, box) position; 0 for a filtered prediction */
+  int32_t* match_gt;                          /* [P] GT row matched at dist_th_tp, -1 */
+  int32_t* order;                             /* [P] (sample, box) position of each sorted prediction, by class */
+  int32_t* counts;                            /* [2][C] kept predictions, kept GT (npos) */
+  int32_t* status;                            /* OR-ed UD_NUS_ST_* bits */
+} UdNusEvalIo;
+
+int ud_nus_pred_to_global(const float* boxes, int64_t n, int ncol, const float* scores, const int64_t* labels,
+                          const int32_t* batch_off, int B, const double* l2g, int num_classes,
+                          const int32_t* attr_moving_host, const int32_t* attr_still_host, double* rec, int32_t* cls,
+                          int32_t* attr, int32_t* status, ud_stream_t stream);
+size_t ud_nus_eval_workspace_bytes(int64_t P, int num_classes);
+int ud_nus_eval(const UdNusCfg* cfg_host, const UdNusEvalIo* io_host, int S, int64_t P, void* workspace,
+                size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
