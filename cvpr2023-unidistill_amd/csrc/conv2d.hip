@@ -1025,11 +1025,7 @@ int launch_wgrad1x1(const void* x, const void* dy, float* partial, long long P, 
                     const Wgrad1x1Plan& pl, const PixMap& xmap, const PixMap& ymap, hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * 64 * (NT + CT) * 2;
   static UdDeviceOnce set;
-  if (const unsigned long long set_bit = set.pending()) {
-    UD_HIP_TRY(hipFuncSetAttribute((const void*)k_conv1x1_wgrad_dma<NT, CT>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    set.mark(set_bit);
-  }
+  if (const int e = ud_allow_dyn_lds(set, (int)lds, k_conv1x1_wgrad_dma<NT, CT>)) return e;
   k_conv1x1_wgrad_dma<NT, CT><<<dim3(pl.slices, pl.n_tiles * pl.c_tiles), 256, lds, stream>>>(
       (const unsigned short*)x, (const unsigned short*)dy, partial, P, Cin, Cout, pl.c_tiles, pl.steps_per_slice,
       xmap, ymap);
@@ -1250,11 +1246,7 @@ extern "C" int ud_conv3x3_wgrad_nhwc_bf16(const void* x, const void* dy, float* 
     int per;
     const int S = wgrad_dma_slices(B, H, W, Cin, Cout, &per);
     static UdDeviceOnce set_dma;
-    if (const unsigned long long set_dma_bit = set_dma.pending()) {
-      UD_HIP_TRY(hipFuncSetAttribute((const void*)k_conv3x3_wgrad_taps, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)kWgradDmaLds));
-      set_dma.mark(set_dma_bit);
-    }
+    if (const int e = ud_allow_dyn_lds(set_dma, (int)kWgradDmaLds, k_conv3x3_wgrad_taps)) return e;
     UdProfScope prof("conv2d.k_wgrad_dma", stream);
     k_conv3x3_wgrad_taps<<<dim3(S, ud_div_up(Cout, 64) * (Cin / 64)), 256, kWgradDmaLds, stream>>>(
         (const unsigned short*)x, (const unsigned short*)dy, partial, gd, Cin / 64, per);
@@ -1272,10 +1264,7 @@ extern "C" int ud_conv3x3_wgrad_nhwc_bf16(const void* x, const void* dy, float* 
   if (CT == 128) {
     const size_t lds = (size_t)2 * kWP * (144 + 144) * 2;
     static UdDeviceOnce set128;
-    if (const unsigned long long set128_bit = set128.pending()) {
-      UD_HIP_TRY(hipFuncSetAttribute((const void*)k_conv3x3_wgrad<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      set128.mark(set128_bit);
-    }
+    if (const int e = ud_allow_dyn_lds(set128, (int)lds, k_conv3x3_wgrad<128>)) return e;
     k_conv3x3_wgrad<128><<<grid, 256, lds, stream>>>((const unsigned short*)x, (const unsigned short*)dy, partial, gm, c_tiles, n_tiles);
   } else {
     const size_t lds = (size_t)2 * kWP * (144 + 80) * 2;

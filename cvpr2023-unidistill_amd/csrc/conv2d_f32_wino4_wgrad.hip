@@ -565,10 +565,7 @@ extern "C" int ud_conv3x3_wino4_wgrad_nhwc_f32(const float* x, const float* dy, 
   if (p.nb > 65535 || p.cb > 65535) return UD_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   static UdDeviceOnce attr_set;
-  if (const unsigned long long attr_set_bit = attr_set.pending()) {
-    UD_HIP_TRY(hipFuncSetAttribute((const void*)k_wino4_wgrad_f32, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
-    attr_set.mark(attr_set_bit);
-  }
+  if (const int e = ud_allow_dyn_lds(attr_set, (int)kSmem, k_wino4_wgrad_f32)) return e;
   UdProfScope prof("conv2d.k_wgrad_wino4_f32", stream);
   float* partial = static_cast<float*>(workspace);
   G4Geom gm{B, H, W, Cin, Cout, p.TY, p.SX, p.nstages, p.sps};

@@ -337,10 +337,7 @@ extern "C" int ud_conv3x3_wino_wgrad_nhwc_f32(const float* x, const float* dy, f
     return UD_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   static UdDeviceOnce attr_set;
-  if (const unsigned long long attr_set_bit = attr_set.pending()) {
-    UD_HIP_TRY(hipFuncSetAttribute((const void*)k_wino_wgrad_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes));
-    attr_set.mark(attr_set_bit);
-  }
+  if (const int e = ud_allow_dyn_lds(attr_set, (int)(2 * kBufBytes), k_wino_wgrad_f32)) return e;
   UdProfScope prof("conv2d.k_wgrad_wino_f32", stream);
   float* partial = static_cast<float*>(workspace);
   WwGeom gm{B, H, W, Cin, Cout, p.TX, p.TY, p.ntiles, p.nstages, p.sps};

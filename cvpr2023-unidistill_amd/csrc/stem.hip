@@ -207,11 +207,7 @@ extern "C" int ud_stem_conv7x7_bn_relu(const float* x, int64_t sb, int64_t sc, i
   const long long ntiles = (long long)B * gm.tiles_y * gm.tiles_x;
   if (ntiles >= (1ll << 31)) return UD_ERR_INVALID_ARG;
   static UdDeviceOnce attr_set;
-  if (const unsigned long long attr_set_bit = attr_set.pending()) {
-    UD_HIP_TRY(hipFuncSetAttribute((const void*)k_stem_conv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
-    UD_HIP_TRY(hipFuncSetAttribute((const void*)k_stem_conv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
-    attr_set.mark(attr_set_bit);
-  }
+  if (const int e = ud_allow_dyn_lds(attr_set, (int)kStemLds, k_stem_conv<false>, k_stem_conv<true>)) return e;
   UdProfScope prof("stem.k_stem_conv", stream);
   const int grid = (int)(ntiles < 512 ? ntiles : 512);          // persistent: two workgroups per CU keep the filters in LDS
   if (out_bf16) k_stem_conv<true><<<grid, 256, kStemLds, stream>>>(x, packed_w, scale, shift, y, gm);

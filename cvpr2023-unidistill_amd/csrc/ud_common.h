@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <atomic>
+#include <initializer_list>
 #include "unidistill_hip.h"
 
 #define UD_WAVE 64
@@ -68,6 +69,21 @@ struct UdDeviceOnce {
   }
   void mark(unsigned long long b) { done.fetch_or(b, std::memory_order_release); }
 };
+
+// Allow the given kernels (one launcher's variants share a guard) `bytes` of dynamic LDS: above the 64 KiB default a
+// launch fails unless the kernel's limit was raised, once per device.  The limit stays what the FIRST call asked for,
+// so `bytes` must be the largest request the launcher can make, not this call's.
+//   static UdDeviceOnce once;  if (const int e = ud_allow_dyn_lds(once, bytes, k_a<...>, k_b<...>)) return e;
+template <typename... Kernels>
+static inline int ud_allow_dyn_lds(UdDeviceOnce& once, int bytes, Kernels... kernels) {
+  if (bytes <= 64 * 1024) return UD_OK;
+  const unsigned long long bit = once.pending();
+  if (!bit) return UD_OK;
+  for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return UD_ERR_HIP;
+  once.mark(bit);
+  return UD_OK;
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int ud_lane() { return threadIdx.x & (UD_WAVE - 1); }

@@ -15,7 +15,7 @@ CSRC = os.path.join(ROOT, "cvpr2023-unidistill_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # the translation units that issue LDS reads from inline asm
 UNITS = ["conv2d_f32_wgrad", "conv2d_f32_1x1p", "conv2d_f32_wino4", "conv2d_f32_wino4_wgrad", "conv2d_f32_wino", "conv2d_f32_wino_wgrad",
-         "conv2d", "spconv_conv"]
+         "conv2d", "spconv_conv", "spconv_wgrad"]
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -384,3 +384,61 @@ def test_mask_order_vs_numpy(M, K):
     ref = np.argsort(mask, kind="stable")
     assert order.dtype == np.int32 and np.array_equal(order, ref)
     assert sp.mask_order(nbr, True) is sp.mask_order(nbr, False)          # cached on the rulebook, shared with the mirrored pass
+
+
+_LDS_LIMIT_CHILD = r'''
+import sys
+sys.path[:0] = [{root!r}, {pkg!r}]
+import numpy as np
+import torch
+import oracle
+from unidistill_amd.ops import spconv as sp
+
+C, MOUT = 128, 300
+
+
+def bf16(a):
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).reshape(a.shape)
+
+
+def check(K, algo):
+    rng = np.random.default_rng(1000 * K + algo)
+    nbr = np.where(rng.random((MOUT, K)) < 0.3, rng.integers(0, MOUT, (MOUT, K)), -1).astype(np.int32)
+    x = rng.standard_normal((MOUT, C)).astype(np.float32)
+    W = (rng.standard_normal((C, K, C)) / np.sqrt(K * C)).astype(np.float32)
+    d = lambda a: None if a is None else torch.from_numpy(a).cuda()
+    if algo == 0:      # data gradient: W read with n / c swapped -> k_conv_mfma_v2<128, 128, true, false>
+        y = sp._conv(d(x), d(nbr), d(W), (1, C, K * C), True, None, C, C, algo=0)
+        ref = oracle.spconv_conv(x, nbr, W, mirror=True, transpose=True)
+    else:              # algo 3 on fp32 tensors -> k_conv_mfma_bf16<128, 128>
+        bias = rng.standard_normal(C).astype(np.float32)
+        y = sp._conv(d(x), d(nbr), d(W), (K * C, C, 1), False, d(bias), C, C, algo=3)
+        ref = oracle.spconv_conv(bf16(x), nbr, bf16(W), bias)
+    torch.cuda.synchronize()
+    np.testing.assert_allclose(y.cpu().numpy(), ref, rtol=2e-5, atol=2e-5 * max(1.0, float(np.abs(ref).max())))
+
+
+check(3, 0)       # the small request first: it must not pin the kernel's dynamic-LDS limit ...
+check(27, 0)      # ... below what the 27-offset launch of the same kernel needs
+check(3, 3)
+check(27, 3)
+print("LDS_LIMIT_OK")
+'''
+
+
+def test_small_K_launch_first_does_not_pin_the_dynamic_lds_limit(hip_lib, tmp_path):
+    """The 128-row kernels' dynamic-LDS request grows with the rulebook width K, and the per-kernel limit is raised once per
+    process: in a FRESH process a 128 -> 128 layer runs with K = 3 and then with K = 27 (153 KB) through the same kernel, on
+    the fp32 data-gradient route and on the bf16-MFMA route; each result is checked against the oracle (fp32 tolerance of
+    test_conv_dgrad_wgrad_vs_oracle; algo 3 against the oracle on bf16-rounded operands)."""
+    import os
+    import subprocess
+    import sys
+    from conftest import PKG, ROOT
+    path = tmp_path / "lds_limit.py"
+    path.write_text(_LDS_LIMIT_CHILD.format(root=ROOT, pkg=PKG))
+    res = subprocess.run([sys.executable, str(path)], cwd=ROOT, env=dict(os.environ, UD_STRICT="1"), capture_output=True,
+                         text=True, timeout=300)
+    assert res.returncode == 0 and "LDS_LIMIT_OK" in res.stdout, res.stdout[-1000:] + res.stderr[-3000:]
