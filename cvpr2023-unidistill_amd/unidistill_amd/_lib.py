@@ -212,6 +212,9 @@ _SIGS = {
                            + [c_void_p] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ud_head_tail_fwd": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "ud_head_tail_bwd": (c_int, [c_void_p] * 11 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "ud_optim_chunk_elems": (c_int, []),
+    "ud_optim_sqnorm": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
+    "ud_optim_clip_adamw": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [ctypes.c_double] * 5 + [c_int, c_void_p]),
 }
 
 

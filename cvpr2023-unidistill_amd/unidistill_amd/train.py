@@ -238,11 +238,21 @@ class Trainer:
 
     configure_optimizers of the reference (BEVFusion_nuscenes_base_exp.py:436-441) returns
     ``[AdamW(lr, weight_decay=1e-7)], [MultiStepLR(optimizer, [10, 15])]``; Lightning steps such a scheduler
-    once per EPOCH: ``epoch_end()`` here is that hook (``lr_milestones=None`` disables it)."""
+    once per EPOCH: ``epoch_end()`` here is that hook (``lr_milestones=None`` disables it).
+
+    ``optimizer="torch"`` (default) clips with ``clip_grad_norm_`` and steps ``torch.optim.AdamW(fused=True)``;
+    ``optimizer="hip"`` (or ``UD_OPTIM=hip`` with the keyword left alone) does both in ``ops.optim.ClipAdamW``'s two
+    launches, skips a step whose gradient norm is not finite (``self.opt.skipped``) and leaves ``p.grad`` unclipped.
+    Checkpoints of the two are interchangeable."""
 
     def __init__(self, step_module, lr=2e-4, weight_decay=1e-7, grad_clip=0.1, device=None,
                  bucket_cap_mb=64, autocast_dtype=None, channels_last=False, lr_milestones=(10, 15),
-                 lr_gamma=0.1):
+                 lr_gamma=0.1, optimizer=None):
+        if optimizer is None:
+            optimizer = os.environ.get("UD_OPTIM", "torch")
+        if optimizer not in ("torch", "hip"):
+            raise ValueError(f"optimizer must be 'torch' or 'hip', got {optimizer!r}")
+        self.optimizer = optimizer
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.module = step_module.to(self.device)
         if channels_last:
@@ -270,7 +280,11 @@ class Trainer:
             # stays on by writing into the bucket views and joining per bucket in a communication hook (ops/wgrad_stream.py)
             if wgrad_stream.ENABLED and self.device.type == "cuda":
                 wgrad_stream.attach_ddp(self.ddp)
-        self.opt = torch.optim.AdamW(trainable, lr=lr, weight_decay=weight_decay, fused=True)
+        if optimizer == "hip":
+            from .ops.optim import ClipAdamW
+            self.opt = ClipAdamW(trainable, lr=lr, weight_decay=weight_decay, max_norm=grad_clip or None)
+        else:
+            self.opt = torch.optim.AdamW(trainable, lr=lr, weight_decay=weight_decay, fused=True)
         self.scheduler = None
         if lr_milestones:
             self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.opt, list(lr_milestones), gamma=lr_gamma)
@@ -289,6 +303,9 @@ class Trainer:
             out = fn(batch)
         out["loss"].backward()
         wgrad_stream.join()                        # (already done by the engine callback of ops/wgrad_stream.py; idempotent)
+        if self.optimizer == "hip":
+            self.opt.step()                        # clip + AdamW + bad-gradient guard in two launches (ops/optim.py)
+            return out
         if self.grad_clip:
             torch.nn.utils.clip_grad_norm_(self.params, self.grad_clip, foreach=True)
         self.opt.step()

@@ -1017,6 +1017,40 @@ size_t ud_nus_eval_workspace_bytes(int64_t P, int num_classes);
 int ud_nus_eval(const UdNusCfg* cfg_host, const UdNusEvalIo* io_host, int S, int64_t P, void* workspace,
                 size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- optimizer: gradient-norm clip + decoupled-weight-decay AdamW in two launches (csrc/optim.hip) ----
+ * The parameter set is cut into chunks of ud_optim_chunk_elems() elements; a chunk lies inside one tensor (the last
+ * chunk of a tensor is short).  One workgroup per chunk; nothing in the grid depends on the data.
+ *   ud_optim_sqnorm      partial[c] = sum of g*g over chunk c (0 for a tensor whose gradient pointer is NULL), in a fixed
+ *                        order that depends on the position inside the chunk only; workgroup 0 also latches
+ *                        state[STEP] into state[STEP_IN].
+ *   ud_optim_clip_adamw  every workgroup sums the partials in the same order, so all of them hold the same total:
+ *                        total_norm = sqrt(sum), coef = min(1, max_norm / (total_norm + 1e-6)), then AdamW on its own
+ *                        chunk with g' = coef * g applied on the fly (gradients are never written).  With skip_nonfinite
+ *                        and a non-finite total_norm nothing is written to params / exp_avg / exp_avg_sq, STEP stays and
+ *                        SKIPPED is incremented.  Workgroup 0 writes STEP, NORM, COEF, SKIPPED, FINITE.
+ * params / exp_avg / exp_avg_sq / grads are DEVICE arrays of per-tensor device pointers (fp32 data, each tensor's
+ * elements in the same storage order in all four).  state is UD_OPTIM_STATE_DOUBLES doubles on the device. */
+typedef struct {
+  int64_t offset;                             /* first element of the chunk inside its tensor */
+  int32_t tensor;                             /* index into the pointer arrays */
+  int32_t length;                             /* 1 .. ud_optim_chunk_elems() */
+} UdOptimChunk;
+#define UD_OPTIM_ST_LR 0                      /* written by the host */
+#define UD_OPTIM_ST_STEP 1                    /* completed (not skipped) steps */
+#define UD_OPTIM_ST_STEP_IN 2                 /* STEP as latched by ud_optim_sqnorm */
+#define UD_OPTIM_ST_NORM 3                    /* total_norm of the last call */
+#define UD_OPTIM_ST_COEF 4                    /* clip coefficient of the last call */
+#define UD_OPTIM_ST_SKIPPED 5                 /* calls skipped by the guard */
+#define UD_OPTIM_ST_FINITE 6                  /* 1 if the last total_norm was finite */
+#define UD_OPTIM_STATE_DOUBLES 8
+int ud_optim_chunk_elems(void);
+int ud_optim_sqnorm(const UdOptimChunk* chunks, int n_chunks, const float* const* grads, double* partial,
+                    double* state, ud_stream_t stream);
+int ud_optim_clip_adamw(const UdOptimChunk* chunks, int n_chunks, float* const* params, float* const* exp_avg,
+                        float* const* exp_avg_sq, const float* const* grads, const double* partial, double* state,
+                        double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                        int skip_nonfinite, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
