@@ -8,6 +8,10 @@
 // exact there), and the per-chunk partials are re-reduced by EVERY workgroup of the second launch in one fixed order:
 // all workgroups derive the identical total_norm / coef / finite flag without a third launch or a grid barrier.
 // No atomics anywhere.
+//
+// Optional weight EMA (ud_optim_clip_adamw_ema): the update kernel carries a fifth stream e and, with the fresh p still in
+// a register, does e = lerp(e, p, w).  w comes from the same device-side step count as the bias corrections, so a step the
+// guard skips neither moves e nor advances a warm-up ramp.  ud_optim_swap exchanges two rows of tensors over the same table.
 #include "ud_common.h"
 #include "ud_prof.h"
 #include <math.h>
@@ -108,6 +112,8 @@ struct StepScalars {
   float coef, wd_mul, w1, beta2, omb2, step_size, bc2_sqrt, eps;
   int lerp_low;                                  // torch's lerp: a + w * (b - a) for w < 0.5, b - (b - a) * (1 - w) otherwise
   float beta1;
+  float ema_w, ema_omw;                          // EMA: e = lerp(e, p, ema_w); ema_omw = 1 - ema_w in fp32, as torch forms it
+  int ema_low;
 };
 
 __device__ __forceinline__ void adamw_one(float& p, float& m, float& v, float g, const StepScalars& s) {
@@ -120,14 +126,24 @@ __device__ __forceinline__ void adamw_one(float& p, float& m, float& v, float g,
   p = p - (s.step_size * m) / denom;
 }
 
-template <bool ALIGNED>
+// torch's lerp(e, p, w), with p the value about to be stored
+__device__ __forceinline__ void ema_one(float& e, float p, const StepScalars& s) {
+  const float d = p - e;
+  e = s.ema_low ? e + s.ema_w * d : p - d * s.ema_omw;
+}
+
+// ea: the chunk's EMA stream (EMA only; otherwise never dereferenced)
+template <bool ALIGNED, bool EMA>
 __device__ __forceinline__ void chunk_adamw(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                            const float* __restrict__ g, int len, const StepScalars& s) {
+                                            float* __restrict__ ea, const float* __restrict__ g, int len,
+                                            const StepScalars& s) {
   const int n4 = len >> 2;
   for (int i = threadIdx.x; i < n4; i += UD_OPTIM_THREADS) {
     const size_t e = 4 * (size_t)i;
     const float4 g4 = ld4<ALIGNED>(g + e);
     float4 p4 = ld4<ALIGNED>(p + e), m4 = ld4<ALIGNED>(m + e), v4 = ld4<ALIGNED>(v + e);
+    float4 e4;
+    if (EMA) e4 = ld4<ALIGNED>(ea + e);
     adamw_one(p4.x, m4.x, v4.x, g4.x, s);
     adamw_one(p4.y, m4.y, v4.y, g4.y, s);
     adamw_one(p4.z, m4.z, v4.z, g4.z, s);
@@ -135,6 +151,13 @@ __device__ __forceinline__ void chunk_adamw(float* __restrict__ p, float* __rest
     st4<ALIGNED>(p + e, p4);
     st4<ALIGNED>(m + e, m4);
     st4<ALIGNED>(v + e, v4);
+    if (EMA) {
+      ema_one(e4.x, p4.x, s);
+      ema_one(e4.y, p4.y, s);
+      ema_one(e4.z, p4.z, s);
+      ema_one(e4.w, p4.w, s);
+      st4<ALIGNED>(ea + e, e4);
+    }
   }
   const int tail = 4 * n4 + threadIdx.x;
   if (tail < len) {
@@ -143,18 +166,67 @@ __device__ __forceinline__ void chunk_adamw(float* __restrict__ p, float* __rest
     p[tail] = pp;
     m[tail] = mm;
     v[tail] = vv;
+    if (EMA) {
+      float ee = ea[tail];
+      ema_one(ee, pp, s);
+      ea[tail] = ee;
+    }
+  }
+}
+
+// A tensor without a gradient is not stepped, but its average still moves towards its (unchanged) value.
+template <bool ALIGNED>
+__device__ __forceinline__ void chunk_ema(const float* __restrict__ p, float* __restrict__ ea, int len,
+                                          const StepScalars& s) {
+  const int n4 = len >> 2;
+  for (int i = threadIdx.x; i < n4; i += UD_OPTIM_THREADS) {
+    const size_t e = 4 * (size_t)i;
+    const float4 p4 = ld4<ALIGNED>(p + e);
+    float4 e4 = ld4<ALIGNED>(ea + e);
+    ema_one(e4.x, p4.x, s);
+    ema_one(e4.y, p4.y, s);
+    ema_one(e4.z, p4.z, s);
+    ema_one(e4.w, p4.w, s);
+    st4<ALIGNED>(ea + e, e4);
+  }
+  const int tail = 4 * n4 + threadIdx.x;
+  if (tail < len) {
+    float ee = ea[tail];
+    ema_one(ee, p[tail], s);
+    ea[tail] = ee;
+  }
+}
+
+// Exact exchange of two streams: moves only, no arithmetic.
+template <bool ALIGNED>
+__device__ __forceinline__ void chunk_swap(float* __restrict__ a, float* __restrict__ b, int len) {
+  const int n4 = len >> 2;
+  for (int i = threadIdx.x; i < n4; i += UD_OPTIM_THREADS) {
+    const size_t e = 4 * (size_t)i;
+    const float4 a4 = ld4<ALIGNED>(a + e), b4 = ld4<ALIGNED>(b + e);
+    st4<ALIGNED>(a + e, b4);
+    st4<ALIGNED>(b + e, a4);
+  }
+  const int tail = 4 * n4 + threadIdx.x;
+  if (tail < len) {
+    const float aa = a[tail], bb = b[tail];
+    a[tail] = bb;
+    b[tail] = aa;
   }
 }
 
 struct Hyper {
   double beta1, beta2, eps, weight_decay, max_norm;
   int skip_nonfinite;
+  double ema_decay, ema_ramp;                    // EMA only; ema_ramp <= 0: constant decay
 };
 
+template <bool EMA>
 __global__ __launch_bounds__(UD_OPTIM_THREADS) void k_optim_clip_adamw(
     const UdOptimChunk* __restrict__ chunks, int n_chunks, float* const* __restrict__ params,
-    float* const* __restrict__ exp_avg, float* const* __restrict__ exp_avg_sq, const float* const* __restrict__ grads,
-    const double* __restrict__ partial, double* __restrict__ state, const Hyper h) {
+    float* const* __restrict__ exp_avg, float* const* __restrict__ exp_avg_sq, float* const* __restrict__ ema,
+    const float* const* __restrict__ grads, const double* __restrict__ partial, double* __restrict__ state,
+    const Hyper h) {
   __shared__ double red[UD_OPTIM_THREADS / UD_WAVE];
   __shared__ StepScalars sh;
   __shared__ int sh_skip;
@@ -183,6 +255,13 @@ __global__ __launch_bounds__(UD_OPTIM_THREADS) void k_optim_clip_adamw(
     sh.step_size = (float)(lr / bc1);
     sh.bc2_sqrt = (float)sqrt(bc2);
     sh.eps = (float)h.eps;
+    if (EMA) {
+      // step counts APPLIED steps, this one included: a skipped step does not advance the ramp
+      const double decay = h.ema_ramp > 0.0 ? h.ema_decay * (1.0 - exp(-step / h.ema_ramp)) : h.ema_decay;
+      sh.ema_w = (float)(1.0 - decay);
+      sh.ema_omw = 1.0f - sh.ema_w;
+      sh.ema_low = sh.ema_w < 0.5f;
+    }
     sh_skip = skip;
     if (blockIdx.x == 0) {                       // the state block has one writer; plain (vector) stores
       state[UD_OPTIM_ST_NORM] = (double)total_norm;
@@ -195,19 +274,40 @@ __global__ __launch_bounds__(UD_OPTIM_THREADS) void k_optim_clip_adamw(
     }
   }
   __syncthreads();
-  if (sh_skip) return;                           // guard: no workgroup touches p, m or v
+  if (sh_skip) return;                           // guard: no workgroup touches p, m, v or the EMA
   const UdOptimChunk c = chunks[blockIdx.x];
   const float* gt = grads[c.tensor];
-  if (gt == nullptr) return;                     // a parameter without a gradient is left alone, as torch does
   const StepScalars s = sh;
   float* p = params[c.tensor] + c.offset;
+  float* ea = EMA ? ema[c.tensor] + c.offset : nullptr;
+  if (gt == nullptr) {                           // a parameter without a gradient is left alone, as torch does
+    if (EMA) {
+      if (aligned16(p) && aligned16(ea))
+        chunk_ema<true>(p, ea, c.length, s);
+      else
+        chunk_ema<false>(p, ea, c.length, s);
+    }
+    return;
+  }
   float* m = exp_avg[c.tensor] + c.offset;
   float* v = exp_avg_sq[c.tensor] + c.offset;
   const float* g = gt + c.offset;
-  if (aligned16(p) && aligned16(m) && aligned16(v) && aligned16(g))
-    chunk_adamw<true>(p, m, v, g, c.length, s);
+  if (aligned16(p) && aligned16(m) && aligned16(v) && aligned16(g) && (!EMA || aligned16(ea)))
+    chunk_adamw<true, EMA>(p, m, v, ea, g, c.length, s);
   else
-    chunk_adamw<false>(p, m, v, g, c.length, s);
+    chunk_adamw<false, EMA>(p, m, v, ea, g, c.length, s);
+}
+
+__global__ __launch_bounds__(UD_OPTIM_THREADS) void k_optim_swap(const UdOptimChunk* __restrict__ chunks,
+                                                                  float* const* __restrict__ a_ptrs,
+                                                                  float* const* __restrict__ b_ptrs) {
+  const UdOptimChunk c = chunks[blockIdx.x];
+  float* a = a_ptrs[c.tensor] + c.offset;
+  float* b = b_ptrs[c.tensor] + c.offset;
+  if (aligned16(a) && aligned16(b))
+    chunk_swap<true>(a, b, c.length);
+  else
+    chunk_swap<false>(a, b, c.length);
 }
 
 }  // namespace
@@ -236,9 +336,41 @@ extern "C" int ud_optim_clip_adamw(const UdOptimChunk* chunks, int n_chunks, flo
   if (n_chunks == 0) return UD_OK;
   hipStream_t stream = (hipStream_t)stream_;
   UdProfScope prof("optim.k_clip_adamw", stream);
-  const Hyper h = {beta1, beta2, eps, weight_decay, max_norm, skip_nonfinite != 0};
-  k_optim_clip_adamw<<<n_chunks, UD_OPTIM_THREADS, 0, stream>>>(chunks, n_chunks, params, exp_avg, exp_avg_sq, grads,
-                                                               partial, state, h);
+  const Hyper h = {beta1, beta2, eps, weight_decay, max_norm, skip_nonfinite != 0, 0.0, 0.0};
+  k_optim_clip_adamw<false><<<n_chunks, UD_OPTIM_THREADS, 0, stream>>>(chunks, n_chunks, params, exp_avg, exp_avg_sq,
+                                                                      nullptr, grads, partial, state, h);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
+}
+
+extern "C" int ud_optim_clip_adamw_ema(const UdOptimChunk* chunks, int n_chunks, float* const* params,
+                                       float* const* exp_avg, float* const* exp_avg_sq, float* const* ema,
+                                       const float* const* grads, const double* partial, double* state, double beta1,
+                                       double beta2, double eps, double weight_decay, double max_norm,
+                                       int skip_nonfinite, double ema_decay, double ema_ramp, ud_stream_t stream_) {
+  if (n_chunks < 0 ||
+      (n_chunks > 0 && (!chunks || !params || !exp_avg || !exp_avg_sq || !ema || !grads || !partial)) || !state)
+    return UD_ERR_INVALID_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(max_norm > 0.0))
+    return UD_ERR_INVALID_ARG;
+  if (!(ema_decay > 0.0 && ema_decay < 1.0) || ema_ramp != ema_ramp) return UD_ERR_INVALID_ARG;
+  if (n_chunks == 0) return UD_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  UdProfScope prof("optim.k_clip_adamw_ema", stream);
+  const Hyper h = {beta1, beta2, eps, weight_decay, max_norm, skip_nonfinite != 0, ema_decay, ema_ramp};
+  k_optim_clip_adamw<true><<<n_chunks, UD_OPTIM_THREADS, 0, stream>>>(chunks, n_chunks, params, exp_avg, exp_avg_sq, ema,
+                                                                     grads, partial, state, h);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
+}
+
+extern "C" int ud_optim_swap(const UdOptimChunk* chunks, int n_chunks, float* const* a_ptrs, float* const* b_ptrs,
+                             ud_stream_t stream_) {
+  if (n_chunks < 0 || (n_chunks > 0 && (!chunks || !a_ptrs || !b_ptrs))) return UD_ERR_INVALID_ARG;
+  if (n_chunks == 0) return UD_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  UdProfScope prof("optim.k_swap", stream);
+  k_optim_swap<<<n_chunks, UD_OPTIM_THREADS, 0, stream>>>(chunks, a_ptrs, b_ptrs);
   UD_LAUNCH_CHECK();
   return UD_OK;
 }

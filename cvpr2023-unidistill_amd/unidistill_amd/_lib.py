@@ -215,6 +215,9 @@ _SIGS = {
     "ud_optim_chunk_elems": (c_int, []),
     "ud_optim_sqnorm": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
     "ud_optim_clip_adamw": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [ctypes.c_double] * 5 + [c_int, c_void_p]),
+    "ud_optim_clip_adamw_ema": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [ctypes.c_double] * 5 + [c_int]
+                                + [ctypes.c_double] * 2 + [c_void_p]),
+    "ud_optim_swap": (c_int, [c_void_p, c_int] + [c_void_p] * 3),
 }
 
 

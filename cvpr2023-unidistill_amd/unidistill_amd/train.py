@@ -8,6 +8,7 @@ Host-side work of the reference's step (valid-box python loop with one sync per 
 corners, numpy gaussian mask, reloading the teacher state_dict every step) is replaced by device
 kernels; data parallelism is one process per GPU with DistributedDataParallel over RCCL.
 """
+import contextlib
 import os
 
 import torch
@@ -243,15 +244,22 @@ class Trainer:
     ``optimizer="torch"`` (default) clips with ``clip_grad_norm_`` and steps ``torch.optim.AdamW(fused=True)``;
     ``optimizer="hip"`` (or ``UD_OPTIM=hip`` with the keyword left alone) does both in ``ops.optim.ClipAdamW``'s two
     launches, skips a step whose gradient norm is not finite (``self.opt.skipped``) and leaves ``p.grad`` unclipped.
-    Checkpoints of the two are interchangeable."""
+    Checkpoints of the two are interchangeable.
+
+    ``ema_decay`` (with ``optimizer="hip"`` only; optionally ``ema_ramp``, a warm-up in steps) keeps an exponential moving
+    average of the trainable weights inside ``ClipAdamW``'s update launch, exact with respect to skipped steps;
+    ``ema_weights()`` puts it in the model's place for the length of a ``with`` block, e.g. for ``ValidationStep``."""
 
     def __init__(self, step_module, lr=2e-4, weight_decay=1e-7, grad_clip=0.1, device=None,
                  bucket_cap_mb=64, autocast_dtype=None, channels_last=False, lr_milestones=(10, 15),
-                 lr_gamma=0.1, optimizer=None):
+                 lr_gamma=0.1, optimizer=None, ema_decay=None, ema_ramp=None):
         if optimizer is None:
             optimizer = os.environ.get("UD_OPTIM", "torch")
         if optimizer not in ("torch", "hip"):
             raise ValueError(f"optimizer must be 'torch' or 'hip', got {optimizer!r}")
+        if (ema_decay is not None or ema_ramp is not None) and optimizer != "hip":
+            raise ValueError("the weight EMA lives in ClipAdamW's update kernel: ema_decay / ema_ramp need optimizer='hip' "
+                             f"(got {optimizer!r}); there is no host-side fallback")
         self.optimizer = optimizer
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.module = step_module.to(self.device)
@@ -282,7 +290,8 @@ class Trainer:
                 wgrad_stream.attach_ddp(self.ddp)
         if optimizer == "hip":
             from .ops.optim import ClipAdamW
-            self.opt = ClipAdamW(trainable, lr=lr, weight_decay=weight_decay, max_norm=grad_clip or None)
+            self.opt = ClipAdamW(trainable, lr=lr, weight_decay=weight_decay, max_norm=grad_clip or None,
+                                 ema_decay=ema_decay, ema_ramp=ema_ramp)
         else:
             self.opt = torch.optim.AdamW(trainable, lr=lr, weight_decay=weight_decay, fused=True)
         self.scheduler = None
@@ -292,6 +301,7 @@ class Trainer:
         self.params = trainable
         self.grad_clip = grad_clip
         self.autocast_dtype = autocast_dtype
+        self.ema = ema_decay is not None
 
     def step(self, batch):
         self.opt.zero_grad(set_to_none=True)
@@ -318,14 +328,47 @@ class Trainer:
             self.scheduler.step()
         return self.opt.param_groups[0]["lr"]
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with trainer.ema_weights():`` the module's trainable parameters hold their exponential moving average; on the
+        way out (also by an exception) the training weights are back, bit for bit.  One launch each way.
+
+        BatchNorm running statistics are buffers, not parameters: inside the block they stay the live model's, which is
+        ``AveragedModel(use_buffers=False)``.  The exchange writes through raw pointers and moves no version counter, so
+        the cached weight re-layouts and BatchNorm folds are dropped on entry and on exit."""
+        from .ops import invalidate_caches
+        if not self.ema:
+            raise RuntimeError("Trainer: no EMA is kept (construct with optimizer='hip', ema_decay=...)")
+
+        def drop_caches():
+            safe = [p for p in self.params if getattr(p, "_ud_hooks_stream_safe", False)]
+            invalidate_caches(self.module)
+            for p in safe:                      # the DDP stride hook's marker is no cache: it survives
+                p._ud_hooks_stream_safe = True
+        try:
+            with self.opt.ema_weights():
+                drop_caches()
+                yield
+        finally:                                # after the swap back
+            drop_caches()
+
     def state_dict(self):
-        return {"optimizer": self.opt.state_dict(), "epoch": self.epoch,
-                "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+        state = {"optimizer": self.opt.state_dict(), "epoch": self.epoch,
+                 "scheduler": None if self.scheduler is None else self.scheduler.state_dict()}
+        if self.ema:
+            state["ema"] = self.opt.ema_state_dict()
+        return state
 
     def load_state_dict(self, state):
+        """(The module's own weights are loaded by the caller, before this.)"""
         from .ops import invalidate_caches
         invalidate_caches(self.module)          # cached re-layouts of frozen weights never outlive a (re)load
         self.opt.load_state_dict(state["optimizer"])
+        if self.ema:
+            if state.get("ema") is not None:
+                self.opt.load_ema_state_dict(state["ema"])
+            else:                               # a checkpoint from before the EMA: start the average at the loaded weights
+                self.opt.reset_ema()
         self.epoch = state.get("epoch", 0)
         if self.scheduler is not None and state.get("scheduler") is not None:
             self.scheduler.load_state_dict(state["scheduler"])
@@ -350,12 +393,16 @@ class DetectStep(nn.Module):
 
 class ValidationStep(nn.Module):
     """validation_step of the base experiments (BEVFusion_nuscenes_base_exp.py): the eval forward under no_grad, then
-    the predictions go to a NuScenesDetectionEval on the device (labels start at 1 there; the evaluator subtracts 1)."""
+    the predictions go to a NuScenesDetectionEval on the device (labels start at 1 there; the evaluator subtracts 1).
 
-    def __init__(self, model, evaluator):
+    ``weights``: a zero-argument callable returning a context manager inside which the forward runs, e.g.
+    ``trainer.ema_weights`` to validate with the averaged weights; ``None`` runs the model as it is."""
+
+    def __init__(self, model, evaluator, weights=None):
         super().__init__()
         self.model = model
         self.evaluator = evaluator
+        self.weights = weights
 
     def forward(self, batch, sample_ids, lidar_to_global):
         points = batch.get("points")
@@ -364,7 +411,8 @@ class ValidationStep(nn.Module):
         was_training = self.model.training
         self.model.eval()
         try:
-            with torch.no_grad():
+            weights = contextlib.nullcontext() if self.weights is None else self.weights()
+            with weights, torch.no_grad():
                 out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None)
         finally:
             self.model.train(was_training)

@@ -1028,8 +1028,15 @@ int ud_nus_eval(const UdNusCfg* cfg_host, const UdNusEvalIo* io_host, int S, int
  *                        chunk with g' = coef * g applied on the fly (gradients are never written).  With skip_nonfinite
  *                        and a non-finite total_norm nothing is written to params / exp_avg / exp_avg_sq, STEP stays and
  *                        SKIPPED is incremented.  Workgroup 0 writes STEP, NORM, COEF, SKIPPED, FINITE.
- * params / exp_avg / exp_avg_sq / grads are DEVICE arrays of per-tensor device pointers (fp32 data, each tensor's
- * elements in the same storage order in all four).  state is UD_OPTIM_STATE_DOUBLES doubles on the device. */
+ *   ud_optim_clip_adamw_ema  the same step (bit for bit) with a fifth row of tensors, ema: after an element's new p is
+ *                        formed, ema = lerp(ema, p, w) in torch's form (ema + w * (p - ema) for w < 0.5, p - (p - ema) *
+ *                        (1 - w) otherwise), w = (float)(1 - d), d = ema_decay for ema_ramp <= 0 and ema_decay *
+ *                        (1 - exp(-n / ema_ramp)) otherwise, n = the number of applied steps including this one (STEP
+ *                        after the call).  A skipped step leaves ema untouched and does not advance n.  A tensor whose
+ *                        gradient pointer is NULL is not stepped, but its ema is still lerped towards its value.
+ *   ud_optim_swap        exchanges a_ptrs[t][i] and b_ptrs[t][i] for every element of the table, bit for bit.
+ * params / exp_avg / exp_avg_sq / ema / grads are DEVICE arrays of per-tensor device pointers (fp32 data, each tensor's
+ * elements in the same storage order in all of them).  state is UD_OPTIM_STATE_DOUBLES doubles on the device. */
 typedef struct {
   int64_t offset;                             /* first element of the chunk inside its tensor */
   int32_t tensor;                             /* index into the pointer arrays */
@@ -1050,6 +1057,13 @@ int ud_optim_clip_adamw(const UdOptimChunk* chunks, int n_chunks, float* const* 
                         float* const* exp_avg_sq, const float* const* grads, const double* partial, double* state,
                         double beta1, double beta2, double eps, double weight_decay, double max_norm,
                         int skip_nonfinite, ud_stream_t stream);
+int ud_optim_clip_adamw_ema(const UdOptimChunk* chunks, int n_chunks, float* const* params, float* const* exp_avg,
+                            float* const* exp_avg_sq, float* const* ema, const float* const* grads,
+                            const double* partial, double* state, double beta1, double beta2, double eps,
+                            double weight_decay, double max_norm, int skip_nonfinite, double ema_decay, double ema_ramp,
+                            ud_stream_t stream);
+int ud_optim_swap(const UdOptimChunk* chunks, int n_chunks, float* const* a_ptrs, float* const* b_ptrs,
+                  ud_stream_t stream);
 
 #ifdef __cplusplus
 }
