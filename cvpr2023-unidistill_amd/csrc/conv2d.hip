@@ -23,7 +23,7 @@
 #include "ud_common.h"
 #include "ud_prof.h"
 #include "conv_pixmap.h"
-#include "wgrad_sum.h"
+#include "ud_reduce.h"
 
 namespace {
 
@@ -1251,9 +1251,7 @@ extern "C" int ud_conv3x3_wgrad_nhwc_bf16(const void* x, const void* dy, float* 
     k_conv3x3_wgrad_taps<<<dim3(S, ud_div_up(Cout, 64) * (Cin / 64)), 256, kWgradDmaLds, stream>>>(
         (const unsigned short*)x, (const unsigned short*)dy, partial, gd, Cin / 64, per);
     UD_LAUNCH_CHECK();
-    k_wgrad_sum<<<ud_div_up((long long)(n / 4), 64), 256, 0, stream>>>(partial, S, n, dw);
-    UD_LAUNCH_CHECK();
-    return UD_OK;
+    return ud_wgrad_sum(partial, S, n, dw, stream);
   }
   ConvGeom gm{B, H, W, Cin, Cout, 0, 0, (long long)B * H * W};
   int CT;
@@ -1271,9 +1269,7 @@ extern "C" int ud_conv3x3_wgrad_nhwc_bf16(const void* x, const void* dy, float* 
     k_conv3x3_wgrad<64><<<grid, 256, lds, stream>>>((const unsigned short*)x, (const unsigned short*)dy, partial, gm, c_tiles, n_tiles);
   }
   UD_LAUNCH_CHECK();
-  k_wgrad_sum<<<ud_div_up((long long)(n / 4), 64), 256, 0, stream>>>(partial, S, n, dw);
-  UD_LAUNCH_CHECK();
-  return UD_OK;
+  return ud_wgrad_sum(partial, S, n, dw, stream);
 }
 
 extern "C" size_t ud_conv1x1_wgrad_workspace_bytes(int64_t P, int Cin, int Cout) {
@@ -1297,10 +1293,7 @@ static int wgrad1x1_impl(const void* x, const void* dy, float* dw, int64_t P, in
   else if (pl.ct == 128) rc = launch_wgrad1x1<64, 128>(x, dy, partial, P, Cin, Cout, pl, xmap, ymap, stream);
   else rc = launch_wgrad1x1<64, 64>(x, dy, partial, P, Cin, Cout, pl, xmap, ymap, stream);
   if (rc != UD_OK) return rc;
-  const size_t n = (size_t)Cout * Cin;
-  k_wgrad_sum<<<ud_div_up((long long)(n / 4), 64), 256, 0, stream>>>(partial, pl.slices, n, dw);
-  UD_LAUNCH_CHECK();
-  return UD_OK;
+  return ud_wgrad_sum(partial, pl.slices, (size_t)Cout * Cin, dw, stream);
 }
 
 extern "C" int ud_conv1x1_wgrad_nhwc_bf16(const void* x, const void* dy, float* dw, int64_t P, int Cin, int Cout,

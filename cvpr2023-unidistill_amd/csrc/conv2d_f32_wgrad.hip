@@ -21,7 +21,7 @@
 #include <utility>
 #include "ud_prof.h"
 #include "conv_pixmap.h"
-#include "wgrad_sum.h"
+#include "ud_reduce.h"
 
 namespace {
 

@@ -20,6 +20,7 @@
 //          w2, dw2 [G][kmax][9][64] fp32 (tap = ky*3+kx);  per-channel vectors fp32 [G*64].
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "ud_reduce.h"
 
 namespace {
 
@@ -341,15 +342,6 @@ __global__ __launch_bounds__(256) void k_tail_wgrad(const unsigned short* __rest
   }
 }
 
-__global__ void k_sum_slices(const float* __restrict__ partial, int slices, size_t n,
-                             float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float a = 0.f;
-  for (int s = 0; s < slices; ++s) a += partial[(size_t)s * n + i];
-  out[i] = a;
-}
-
 // ---- input gradient: da = conv^T(dz), ReLU mask, BatchNorm backward --------------------------------
 // MFMA roles: rows = 16 hidden channels (weights, registers), cols = 16 pixels, K = 32 >= 27 (j,tap).
 // Row m of MFMA tile t is channel 32*(t>>1) + 8*(m>>2) + 4*(t&1) + (m&3), so that lane group gq
@@ -556,33 +548,6 @@ __global__ __launch_bounds__(256) void k_tail_bwd(const unsigned short* __restri
   }
 }
 
-// dbeta, dgamma and the per-channel constants of dy = scale*dr + k2*y + k0.
-__global__ void k_bn_bwd_final(const float* __restrict__ partial, int slices, int C, long long P,
-                               const float* __restrict__ scale, const float* __restrict__ mean,
-                               const float* __restrict__ invstd, float* __restrict__ dgamma,
-                               float* __restrict__ dbeta, float* __restrict__ k0,
-                               float* __restrict__ k2) {
-  const int c = blockIdx.x, lane = threadIdx.x;      // one wave per channel, fixed-order reduction
-  float a = 0.f, q = 0.f;
-  for (int s = lane; s < slices; s += 64) {
-    a += partial[((size_t)s * C + c) * 2];
-    q += partial[((size_t)s * C + c) * 2 + 1];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o);
-    q += __shfl_xor(q, o);
-  }
-  if (lane != 0) return;
-  const float is = invstd[c], dg = q * is;
-  dbeta[c] = a;
-  dgamma[c] = dg;
-  const float inv_p = 1.0f / (float)P;
-  const float kk2 = -scale[c] * (dg * inv_p) * is;
-  k2[c] = kk2;
-  k0[c] = -scale[c] * (a * inv_p) - kk2 * mean[c];
-}
-
 bool geom_ok(int B, int H, int W, int G, int kmax) {
   return B > 0 && H > 0 && W > 0 && G > 0 && kmax > 0 && kmax <= kMaxOut &&
          (long long)B * H * W * G * kHC < (1LL << 40);
@@ -684,9 +649,7 @@ int ud_head_tail_bwd(const void* y, const float* dz, const float* w2, const floa
     k_tail_wgrad<<<dim3(kWgradSlices, G), 256, 0, stream>>>((const unsigned short*)y, scale, shift, dz,
                                                             w.wgrad_partial, gm);
     UD_LAUNCH_CHECK();
-    const size_t nW = (size_t)G * kmax * 9 * kHC;
-    k_sum_slices<<<ud_div_up((long long)nW, 256), 256, 0, stream>>>(w.wgrad_partial, kWgradSlices, nW, dw2);
-    UD_LAUNCH_CHECK();
+    if (const int e = ud_slice_sum(w.wgrad_partial, kWgradSlices, (size_t)G * kmax * 9 * kHC, dw2, stream)) return e;
   }
   BwdConst cst{scale, shift, mean, w.k0, w.k2};
   {
@@ -694,9 +657,10 @@ int ud_head_tail_bwd(const void* y, const float* dz, const float* w2, const floa
     k_tail_bwd<false><<<dim3(kBwdSlices, G), 256, 0, stream>>>((const unsigned short*)y, dz, w2, cst,
                                                                nullptr, w.bwd_partial, gm);
     UD_LAUNCH_CHECK();
-    k_bn_bwd_final<<<C, 64, 0, stream>>>(w.bwd_partial, kBwdSlices, C, P, scale, mean,
-                                                           invstd, dgamma, dbeta, w.k0, w.k2);
-    UD_LAUNCH_CHECK();
+    // one accumulator per lane, as the one-wave kernel this replaced: k_bn_bwd_final<64> unrolls four ways only above 192 slices
+    static_assert(kBwdSlices <= 192, "more slices change the order in which ud_bn_bwd_final adds them");
+    if (const int e = ud_bn_bwd_final(w.bwd_partial, kBwdSlices, C, P, scale, mean, invstd, dgamma, dbeta, w.k0, w.k2, stream))
+      return e;
   }
   {
     UdProfScope prof("head_tail.k_dy", stream);

@@ -10,8 +10,11 @@
 //   k_gtail_dgrad  da[q, c] = sum_{tap,k} dz[q - tap, k] * w[k, tap, c]: same lane map, dz window in registers, 16-byte stores
 //   k_gtail_wgrad  dW[k, tap, c] = sum_q a[q, c] * dz[q - tap, k]: the forward's lane map and strip walk, 9 * KM 4-channel accumulators,
 //                  a workgroup walks a slice of the strips; slices are summed in a fixed order (deterministic)
+#include <type_traits>
+
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "ud_reduce.h"
 
 namespace {
 
@@ -169,8 +172,8 @@ __global__ __launch_bounds__(256) void k_gtail_fwd(const float* __restrict__ a, 
 // MODE 0 stores da.  MODE 1 / 2 are the BatchNorm backward of the fused (relu(bn(y)) -> tail) block computed ON the data
 // gradient instead of after it: da is recomputed in both passes and never stored (1.39 GB at B = 4, written once and read
 // twice by the separate kernels).  MODE 1: partial[slice][c] = (sum dr, sum dr * (y - mean)) with dr = da where
-// y * scale + shift > 0; MODE 2: dy = scale * dr + k2 * y + k0 (k0 / k2 from k_gtail_bn_final).  MODE 3 = MODE 2 + the per-channel
-// sums of the dy values it stores (colsum[slice][c]; k_gtail_colsum_final adds the slices in order): the bias gradient of the
+// y * scale + shift > 0; MODE 2: dy = scale * dr + k2 * y + k0 (k0 / k2 from k_bn_bwd_final).  MODE 3 = MODE 2 + the per-channel
+// sums of the dy values it stores (colsum[slice][c]; k_colsum_final adds the slices in order): the bias gradient of the
 // convolution that produced y (center_head.py:339: bias=True in front of the BatchNorm), which otherwise is one more pass
 // over the 1.39 GB gradient (ATen's reduce_kernel ran it on 11 workgroups: 2.1 ms per step).
 struct GTailBn {
@@ -332,81 +335,6 @@ __global__ __launch_bounds__(256) void k_gtail_dgrad(const float* __restrict__ d
   }
 }
 
-// out[c] = sum over the slices of colsum[slice][c]: T threads per channel, four loads in flight per thread, fixed tree
-template <int T>
-__global__ __launch_bounds__(T) void k_gtail_colsum_final(const float* __restrict__ colsum, int slices, int C, float* __restrict__ out) {
-  __shared__ float red[T / 64];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int s = tid;
-  for (; s + 3 * T < slices; s += 4 * T) {
-    const float v0 = colsum[(size_t)s * C + c], v1 = colsum[(size_t)(s + T) * C + c], v2 = colsum[(size_t)(s + 2 * T) * C + c],
-                v3 = colsum[(size_t)(s + 3 * T) * C + c];
-    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-  }
-  for (; s < slices; s += T) a0 += colsum[(size_t)s * C + c];
-  float a = (a0 + a1) + (a2 + a3);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-  if (T > 64) {
-    if (lane == 0) red[wv] = a;
-    __syncthreads();
-    if (tid == 0) {
-      a = red[0];
-#pragma unroll
-      for (int w = 1; w < T / 64; ++w) a += red[w];
-    }
-  }
-  if (tid == 0) out[c] = a;
-}
-
-// dgamma / dbeta and the two per-channel constants of the dy pass (the k_bn_bwd_final of bn_act.hip on this layout)
-template <int T>
-__global__ __launch_bounds__(T) void k_gtail_bn_final(const float* __restrict__ partial, int slices, int C, long long P,
-                                                      const float* __restrict__ scale, const float* __restrict__ mean,
-                                                      const float* __restrict__ invstd, float* __restrict__ dgamma,
-                                                      float* __restrict__ dbeta, float* __restrict__ k0, float* __restrict__ k2) {
-  // T threads per channel, four independent row loads in flight per thread, fixed tree (see k_bn_bwd_final of bn_act.hip)
-  __shared__ float red[T / 64][2];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  auto ld = [&](int s) { return *reinterpret_cast<const float2*>(partial + ((size_t)s * C + c) * 2); };
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-  int s = tid;
-  for (; s + 3 * T < slices; s += 4 * T) {
-    const float2 v0 = ld(s), v1 = ld(s + T), v2 = ld(s + 2 * T), v3 = ld(s + 3 * T);
-    a0 += v0.x; q0 += v0.y;
-    a1 += v1.x; q1 += v1.y;
-    a2 += v2.x; q2 += v2.y;
-    a3 += v3.x; q3 += v3.y;
-  }
-  for (; s < slices; s += T) {
-    const float2 v = ld(s);
-    a0 += v.x; q0 += v.y;
-  }
-  float a = (a0 + a1) + (a2 + a3), q = (q0 + q1) + (q2 + q3);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o);
-    q += __shfl_xor(q, o);
-  }
-  if (T > 64) {
-    if (lane == 0) { red[wv][0] = a; red[wv][1] = q; }
-    __syncthreads();
-    if (tid == 0) {
-      a = red[0][0], q = red[0][1];
-#pragma unroll
-      for (int w = 1; w < T / 64; ++w) { a += red[w][0]; q += red[w][1]; }
-    }
-  }
-  if (tid != 0) return;
-  const float is = invstd[c], dg = q * is, inv_p = 1.0f / (float)P;
-  dbeta[c] = a;
-  dgamma[c] = dg;
-  const float kk2 = -scale[c] * (dg * inv_p) * is;
-  k2[c] = kk2;
-  k0[c] = -scale[c] * (a * inv_p) - kk2 * mean[c];
-}
-
 // partial[slice][g][k][tap][c] = sum over the slice's tiles of a[q, c] * dz[q - (tap - 1), k]
 template <int KM, bool BN>
 __global__ __launch_bounds__(256) void k_gtail_wgrad(const float* __restrict__ a, const float* __restrict__ dz,
@@ -538,19 +466,38 @@ __global__ __launch_bounds__(256) void k_gtail_wgrad(const float* __restrict__ a
   }
 }
 
-__global__ void k_gtail_wsum(const float* __restrict__ partial, int S, long long n, float* __restrict__ dw) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < S; ++k) s += partial[(size_t)k * n + i];
-  dw[i] = s;
-}
-
 bool gtail_ok(int B, int H, int W, int G, int KM) {
   return B > 0 && H > 0 && W > 0 && G > 0 && KM >= 1 && KM <= kKMax &&
          (long long)B * ud_div_up(W, kTW) * ud_div_up(H, kTH) <= 65535;     // tiles ride on grid.y
 }
 int gtail_slices(int ntiles) { return ntiles < 32 ? ntiles : 32; }
+
+// forward, data gradient, BatchNorm backward (a workgroup per strip and group): strips of up to 48 rows, shorter when that leaves
+// fewer than ~8 workgroups per CU
+int gtail_strip_rows(const GTail& t) {
+  int strip_rows = kStripMax;
+  while (strip_rows > kTH && (long long)t.G * t.B * t.tiles_x * ud_div_up(t.H, strip_rows) < 2048) strip_rows -= kTH;
+  return strip_rows;
+}
+// weight gradient (a workgroup per SLICE of the strips and group): shorter only when there are fewer strips than slices
+int gtail_wgrad_strip_rows(const GTail& t) {
+  int strip_rows = kStripMax;
+  while (strip_rows > kTH && t.B * t.tiles_x * ud_div_up(t.H, strip_rows) < 32) strip_rows -= kTH;
+  return strip_rows;
+}
+
+// runtime KM (1 .. kKMax: gtail_ok) -> compile-time constant: f(std::integral_constant<int, KM>)
+// (the callers launch kernel templates from a generic lambda, some through a pointer picked at run time: hipcc 7.2 keeps all 32
+// host stubs of k_gtail_fwd / _dgrad / _wgrad -- after a compiler change compare the object's symbol list, see conv2d_f32_wgrad.hip)
+template <typename F>
+void gtail_with_km(int KM, F f) {
+  switch (KM) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
 
 }  // namespace
 
@@ -560,17 +507,12 @@ static int gtail_fwd_impl(const float* a, const float* bn_scale, const float* bn
   GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
   hipStream_t stream = (hipStream_t)stream_;
   UdProfScope prof("head_tail.k_gtail_fwd", stream);
-  // strips of up to 48 rows, shorter when that leaves fewer than ~8 workgroups per CU
-  int strip_rows = kStripMax;
-  while (strip_rows > kTH && (long long)G * B * t.tiles_x * ud_div_up(H, strip_rows) < 2048) strip_rows -= kTH;
-  const int strips = ud_div_up(H, strip_rows);
+  const int strip_rows = gtail_strip_rows(t), strips = ud_div_up(H, strip_rows);
   const dim3 grid(G, B * t.tiles_x * strips);
-  switch (KM) {
-    case 1: if (bn_scale) k_gtail_fwd<1, true><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); else k_gtail_fwd<1, false><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); break;
-    case 2: if (bn_scale) k_gtail_fwd<2, true><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); else k_gtail_fwd<2, false><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); break;
-    case 3: if (bn_scale) k_gtail_fwd<3, true><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); else k_gtail_fwd<3, false><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); break;
-    default: if (bn_scale) k_gtail_fwd<4, true><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); else k_gtail_fwd<4, false><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift); break;
-  }
+  gtail_with_km(KM, [&](auto km) {
+    const auto k = bn_scale ? k_gtail_fwd<km(), true> : k_gtail_fwd<km(), false>;
+    k<<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift);
+  });
   UD_LAUNCH_CHECK();
   return UD_OK;
 }
@@ -594,33 +536,17 @@ extern "C" int ud_head_tail_f32_dgrad(const float* dz, const float* w, float* da
   GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
   hipStream_t stream = (hipStream_t)stream_;
   UdProfScope prof("head_tail.k_gtail_dgrad", stream);
-  int strip_rows = kStripMax;
-  while (strip_rows > kTH && (long long)G * B * t.tiles_x * ud_div_up(H, strip_rows) < 2048) strip_rows -= kTH;
-  const int strips = ud_div_up(H, strip_rows);
+  const int strip_rows = gtail_strip_rows(t), strips = ud_div_up(H, strip_rows);
   const dim3 grid(G, B * t.tiles_x * strips);
-  const GTailBn none{};
-  switch (KM) {
-    case 1: k_gtail_dgrad<1, 0><<<grid, 256, 0, stream>>>(dz, w, da, t, strip_rows, strips, none); break;
-    case 2: k_gtail_dgrad<2, 0><<<grid, 256, 0, stream>>>(dz, w, da, t, strip_rows, strips, none); break;
-    case 3: k_gtail_dgrad<3, 0><<<grid, 256, 0, stream>>>(dz, w, da, t, strip_rows, strips, none); break;
-    default: k_gtail_dgrad<4, 0><<<grid, 256, 0, stream>>>(dz, w, da, t, strip_rows, strips, none); break;
-  }
+  gtail_with_km(KM, [&](auto km) { k_gtail_dgrad<km(), 0><<<grid, 256, 0, stream>>>(dz, w, da, t, strip_rows, strips, GTailBn{}); });
   UD_LAUNCH_CHECK();
   return UD_OK;
-}
-
-static void gtail_bn_grid(const GTail& t, int* strip_rows, int* strips) {
-  int sr = kStripMax;
-  while (sr > kTH && (long long)t.G * t.B * t.tiles_x * ud_div_up(t.H, sr) < 2048) sr -= kTH;
-  *strip_rows = sr;
-  *strips = ud_div_up(t.H, sr);
 }
 
 extern "C" size_t ud_head_tail_f32_bn_bwd_workspace_bytes(int B, int H, int W, int G, int KM) {
   if (!gtail_ok(B, H, W, G, KM)) return 0;
   GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
-  int strip_rows, strips;
-  gtail_bn_grid(t, &strip_rows, &strips);
+  const int strips = ud_div_up(H, gtail_strip_rows(t));
   const size_t C = (size_t)G * kHC;
   return ud_align_up(((size_t)B * t.tiles_x * strips * C * 3 + 2 * C) * sizeof(float));
 }
@@ -634,8 +560,7 @@ extern "C" int ud_head_tail_f32_bn_bwd(const float* dz, const float* w, const fl
   if (!workspace || workspace_bytes < ud_head_tail_f32_bn_bwd_workspace_bytes(B, H, W, G, KM)) return UD_ERR_WORKSPACE;
   GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
   hipStream_t stream = (hipStream_t)stream_;
-  int strip_rows, strips;
-  gtail_bn_grid(t, &strip_rows, &strips);
+  const int strip_rows = gtail_strip_rows(t), strips = ud_div_up(H, strip_rows);
   const int slices = B * t.tiles_x * strips, C = G * kHC;
   const dim3 grid(G, slices);
   float* partial = (float*)workspace;
@@ -645,43 +570,18 @@ extern "C" int ud_head_tail_f32_bn_bwd(const float* dz, const float* w, const fl
   GTailBn bn{y, bn_scale, bn_shift, mean, k0, k2, partial, colsum};
   {
     UdProfScope prof("head_tail.k_gtail_bn_bwd_reduce", stream);
-    switch (KM) {
-      case 1: k_gtail_dgrad<1, 1><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      case 2: k_gtail_dgrad<2, 1><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      case 3: k_gtail_dgrad<3, 1><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      default: k_gtail_dgrad<4, 1><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-    }
+    gtail_with_km(KM, [&](auto km) { k_gtail_dgrad<km(), 1><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); });
     UD_LAUNCH_CHECK();
-    if (slices > 128)
-      k_gtail_bn_final<256><<<C, 256, 0, stream>>>(partial, slices, C, (long long)B * H * W, bn_scale, mean, invstd, dgamma, dbeta,
-                                                   k0, k2);
-    else
-      k_gtail_bn_final<64><<<C, 64, 0, stream>>>(partial, slices, C, (long long)B * H * W, bn_scale, mean, invstd, dgamma, dbeta,
-                                                 k0, k2);
-    UD_LAUNCH_CHECK();
+    if (const int e = ud_bn_bwd_final(partial, slices, C, (long long)B * H * W, bn_scale, mean, invstd, dgamma, dbeta, k0, k2, stream))
+      return e;
   }
   UdProfScope prof("head_tail.k_gtail_bn_bwd_dx", stream);
-  if (dy_colsum) {
-    switch (KM) {
-      case 1: k_gtail_dgrad<1, 3><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      case 2: k_gtail_dgrad<2, 3><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      case 3: k_gtail_dgrad<3, 3><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-      default: k_gtail_dgrad<4, 3><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-    }
-    UD_LAUNCH_CHECK();
-    if (slices > 128) k_gtail_colsum_final<256><<<C, 256, 0, stream>>>(colsum, slices, C, dy_colsum);
-    else k_gtail_colsum_final<64><<<C, 64, 0, stream>>>(colsum, slices, C, dy_colsum);
-    UD_LAUNCH_CHECK();
-    return UD_OK;
-  }
-  switch (KM) {
-    case 1: k_gtail_dgrad<1, 2><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-    case 2: k_gtail_dgrad<2, 2><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-    case 3: k_gtail_dgrad<3, 2><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-    default: k_gtail_dgrad<4, 2><<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn); break;
-  }
+  gtail_with_km(KM, [&](auto km) {
+    const auto k = dy_colsum ? k_gtail_dgrad<km(), 3> : k_gtail_dgrad<km(), 2>;
+    k<<<grid, 256, 0, stream>>>(dz, w, dy, t, strip_rows, strips, bn);
+  });
   UD_LAUNCH_CHECK();
-  return UD_OK;
+  return dy_colsum ? ud_colsum_final(colsum, slices, C, dy_colsum, stream) : UD_OK;
 }
 
 extern "C" size_t ud_head_tail_f32_wgrad_workspace_bytes(int B, int H, int W, int G, int KM) {
@@ -696,24 +596,18 @@ static int gtail_wgrad_impl(const float* a, const float* bn_scale, const float* 
   if (!workspace || workspace_bytes < ud_head_tail_f32_wgrad_workspace_bytes(B, H, W, G, KM)) return UD_ERR_WORKSPACE;
   GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
   hipStream_t stream = (hipStream_t)stream_;
-  int strip_rows = kStripMax;
-  while (strip_rows > kTH && B * t.tiles_x * ud_div_up(H, strip_rows) < 32) strip_rows -= kTH;
+  const int strip_rows = gtail_wgrad_strip_rows(t);
   const int strips = ud_div_up(H, strip_rows), nstrips = B * t.tiles_x * strips;
   const int S = gtail_slices(nstrips);          // <= the slice count the workspace was sized for (strips <= tiles)
   float* partial = reinterpret_cast<float*>(workspace);
   UdProfScope prof("head_tail.k_gtail_wgrad", stream);
   const dim3 grid(G, S);
-  switch (KM) {
-    case 1: if (bn_scale) k_gtail_wgrad<1, true><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); else k_gtail_wgrad<1, false><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); break;
-    case 2: if (bn_scale) k_gtail_wgrad<2, true><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); else k_gtail_wgrad<2, false><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); break;
-    case 3: if (bn_scale) k_gtail_wgrad<3, true><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); else k_gtail_wgrad<3, false><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); break;
-    default: if (bn_scale) k_gtail_wgrad<4, true><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); else k_gtail_wgrad<4, false><<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift); break;
-  }
+  gtail_with_km(KM, [&](auto km) {
+    const auto k = bn_scale ? k_gtail_wgrad<km(), true> : k_gtail_wgrad<km(), false>;
+    k<<<grid, 256, 0, stream>>>(a, dz, partial, t, strip_rows, strips, nstrips, S, bn_scale, bn_shift);
+  });
   UD_LAUNCH_CHECK();
-  const long long n = (long long)G * KM * 9 * kHC;
-  k_gtail_wsum<<<ud_div_up(n, 256), 256, 0, stream>>>(partial, S, n, dw);
-  UD_LAUNCH_CHECK();
-  return UD_OK;
+  return ud_slice_sum(partial, S, (size_t)G * KM * 9 * kHC, dw, stream);
 }
 
 extern "C" int ud_head_tail_f32_wgrad(const float* a, const float* dz, float* dw, int B, int H, int W, int G,

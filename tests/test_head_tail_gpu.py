@@ -135,7 +135,10 @@ def test_fp32_group_tail_vs_grouped_conv(hip_lib, shape):
         assert (x - y).abs().max() <= 2e-5 * y.abs().max() + 1e-6, name
 
 
-@pytest.mark.parametrize("shape", [(2, 20, 36, 5, 3), (1, 17, 9, 42, 3), (2, 8, 16, 3, 4), (2, 100, 140, 42, 3)])
+# (3, 120, 48, 1, 1): one group falls to 8-row strips, 3 * 3 * 15 = 135 slices > 128 -- the 256-thread form of the two finalize
+# kernels (the real head: B = 4, 180 x 180, G = 42 -> 192 slices)
+@pytest.mark.parametrize("shape", [(2, 20, 36, 5, 3), (1, 17, 9, 42, 3), (2, 8, 16, 3, 4), (2, 100, 140, 42, 3),
+                                   (3, 120, 48, 1, 1)])
 @pytest.mark.parametrize("training", [True, False])
 def test_fp32_bn_relu_group_tail_vs_torch(hip_lib, shape, training):
     """ud_head_tail_f32_bn_fwd / _bn_wgrad (BatchNorm + ReLU applied as the tail kernels load the raw hidden tensor) + the
