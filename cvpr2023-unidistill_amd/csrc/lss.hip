@@ -17,43 +17,7 @@
 namespace {
 
 // ---- per-camera matrices --------------------------------------------------------------------
-// mats[cam] = { inverse(ida) , sensor2ego @ inverse(intrin) , bda }  (3 x 16 floats, row major)
-__device__ bool inv4x4(const float* a, double* o) {
-  double m[4][8];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      m[i][j] = (double)a[i * 4 + j];
-      m[i][4 + j] = (i == j) ? 1.0 : 0.0;
-    }
-  for (int c = 0; c < 4; ++c) {
-    int piv = c;
-    double best = fabs(m[c][c]);
-    for (int r = c + 1; r < 4; ++r)
-      if (fabs(m[r][c]) > best) {
-        best = fabs(m[r][c]);
-        piv = r;
-      }
-    if (best == 0.0) return false;
-    if (piv != c)
-      for (int j = 0; j < 8; ++j) {
-        const double t = m[c][j];
-        m[c][j] = m[piv][j];
-        m[piv][j] = t;
-      }
-    const double inv = 1.0 / m[c][c];
-    for (int j = 0; j < 8; ++j) m[c][j] *= inv;
-    for (int r = 0; r < 4; ++r)
-      if (r != c) {
-        const double f = m[r][c];
-        if (f != 0.0)
-          for (int j = 0; j < 8; ++j) m[r][j] -= f * m[c][j];
-      }
-  }
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) o[i * 4 + j] = m[i][4 + j];
-  return true;
-}
-
+// mats[cam] = { inverse(ida) , sensor2ego @ inverse(intrin) , bda }  (3 x 16 floats, row major); the inverse is ud_inv4x4 (lss_geom.h)
 // Products follow the arithmetic of the reference's CPU path bit for bit: torch's small batched
 // matmul (contraction*rows*cols < 400, aten/native/LinearAlgebra.cpp baddbmm_cpu_kernel) is a plain
 // loop  acc = 0; acc += a[k]*b[k]  in fp32 with separately rounded product and sum (no FMA).
@@ -80,7 +44,7 @@ __global__ void k_prepare_mats(const float* __restrict__ s2e, const float* __res
   if (ida_inv) {
     for (int k = 0; k < 16; ++k) o[k] = ida_inv[(size_t)i * 16 + k];
   } else {
-    if (!inv4x4(ida + (size_t)i * 16, inv))
+    if (!ud_inv4x4(ida + (size_t)i * 16, inv))
       for (int k = 0; k < 16; ++k) inv[k] = __builtin_nan("");
     for (int k = 0; k < 16; ++k) o[k] = (float)inv[k];
   }
@@ -89,7 +53,7 @@ __global__ void k_prepare_mats(const float* __restrict__ s2e, const float* __res
   if (intrin_inv) {
     for (int k = 0; k < 16; ++k) kin[k] = intrin_inv[(size_t)i * 16 + k];
   } else {
-    if (!inv4x4(intrin + (size_t)i * 16, inv))
+    if (!ud_inv4x4(intrin + (size_t)i * 16, inv))
       for (int k = 0; k < 16; ++k) inv[k] = __builtin_nan("");
     for (int k = 0; k < 16; ++k) kin[k] = (float)inv[k];
   }

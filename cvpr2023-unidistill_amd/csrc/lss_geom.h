@@ -58,3 +58,42 @@ __device__ __forceinline__ void ud_frustum_point(const UdFrustum& f, long long g
   *by = (int)__fdiv_rn(__fsub_rn(q[1], f.lo1), f.sz1);
   *bz = (int)__fdiv_rn(__fsub_rn(q[2], f.lo2), f.sz2);
 }
+
+// 4x4 inverse by Gauss-Jordan elimination with partial pivoting in fp64 (a: fp32 or fp64, row major); false for a singular
+// matrix.  Shared by k_prepare_mats (lss.hip) and the LiDAR depth-label projection (depth_sup.hip).
+template <typename T>
+__device__ bool ud_inv4x4(const T* a, double* o) {
+  double m[4][8];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      m[i][j] = (double)a[i * 4 + j];
+      m[i][4 + j] = (i == j) ? 1.0 : 0.0;
+    }
+  for (int c = 0; c < 4; ++c) {
+    int piv = c;
+    double best = fabs(m[c][c]);
+    for (int r = c + 1; r < 4; ++r)
+      if (fabs(m[r][c]) > best) {
+        best = fabs(m[r][c]);
+        piv = r;
+      }
+    if (best == 0.0) return false;
+    if (piv != c)
+      for (int j = 0; j < 8; ++j) {
+        const double t = m[c][j];
+        m[c][j] = m[piv][j];
+        m[piv][j] = t;
+      }
+    const double inv = 1.0 / m[c][c];
+    for (int j = 0; j < 8; ++j) m[c][j] *= inv;
+    for (int r = 0; r < 4; ++r)
+      if (r != c) {
+        const double f = m[r][c];
+        if (f != 0.0)
+          for (int j = 0; j < 8; ++j) m[r][j] -= f * m[c][j];
+      }
+  }
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) o[i * 4 + j] = m[i][4 + j];
+  return true;
+}

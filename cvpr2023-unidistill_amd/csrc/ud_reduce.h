@@ -163,5 +163,39 @@ inline int ud_colsum_final(const float* partial, int slices, int C, float* out, 
   return UD_OK;
 }
 
+// partial[slice] = (sum, count) -> out = (sum / max(1, count), count): a masked mean whose divisor is this call's own count.
+// One workgroup; thread t adds slices t, t + 256, ... in fp64, then a fixed tree, one division, one rounding to fp32: the
+// scalar does not depend on how many slices the pass was cut into beyond the roundings of the partials themselves
+// (the depth-supervision loss of depth_sup.hip).
+__global__ __launch_bounds__(256) void k_mean_final(const float* __restrict__ partial, int slices, float* __restrict__ out) {
+  __shared__ double red[4][2];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double a = 0.0, n = 0.0;
+  for (int s = tid; s < slices; s += 256) {
+    const float2 v = *reinterpret_cast<const float2*>(partial + (size_t)s * 2);
+    a += (double)v.x;
+    n += (double)v.y;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o);
+    n += __shfl_xor(n, o);
+  }
+  if (lane == 0) { red[wv][0] = a; red[wv][1] = n; }
+  __syncthreads();
+  if (tid != 0) return;
+  a = red[0][0], n = red[0][1];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) { a += red[w][0]; n += red[w][1]; }
+  out[0] = (float)(a / (n < 1.0 ? 1.0 : n));
+  out[1] = (float)n;
+}
+
+inline int ud_mean_final(const float* partial, int slices, float* out, hipStream_t stream) {
+  k_mean_final<<<1, 256, 0, stream>>>(partial, slices, out);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
+}
+
 }  // namespace
 #endif  // UD_REDUCE_H_

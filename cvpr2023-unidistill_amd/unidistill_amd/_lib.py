@@ -218,6 +218,12 @@ _SIGS = {
     "ud_optim_clip_adamw_ema": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [ctypes.c_double] * 5 + [c_int]
                                 + [ctypes.c_double] * 2 + [c_void_p]),
     "ud_optim_swap": (c_int, [c_void_p, c_int] + [c_void_p] * 3),
+    "ud_depth_labels_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ud_depth_labels": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int] + [c_void_p] * 4 + [c_int] * 4
+                        + [ctypes.c_double] * 3 + [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ud_depth_loss_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ud_depth_loss_fwd": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ud_depth_loss_bwd": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p] * 4 + [c_i64] * 4 + [c_int] * 4 + [c_void_p]),
 }
 
 

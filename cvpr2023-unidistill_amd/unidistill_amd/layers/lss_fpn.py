@@ -147,13 +147,28 @@ class LSSFPN(nn.Module):
         else:
             bins, _ = self.get_geometry_bins(*geo)
             bev = _lss.lift_splat(depth_feature, bins, B, ncam, D, C, nx, ny, nz)
+        if isinstance(is_return_depth, str):
+            if is_return_depth != "logits":
+                raise ValueError(f"is_return_depth must be False, True or 'logits', got {is_return_depth!r}")
+            return bev, depth_feature[:, :D]        # what ops.depth_sup.depth_loss takes (a view: no copy)
         if is_return_depth:
             return bev, depth_feature[:, :D].softmax(1)
         return bev
 
+    def lidar_depth_labels(self, points, mats_dict):
+        """Depth-bin labels of the key frame from the collated, post-BDA cloud f32[B, Nmax, >= 3] (or a list of per-sample
+        clouds): -> (dmin f32[B, ncam, fH, fW], label i32[B, ncam, fH, fW]), ops.depth_sup.lidar_depth_labels."""
+        from ..ops import depth_sup
+        if isinstance(points, (list, tuple)):
+            points = torch.nn.utils.rnn.pad_sequence(list(points), batch_first=True)
+        return depth_sup.lidar_depth_labels(points, mats_dict["sensor2ego_mats"][:, 0], mats_dict["intrin_mats"][:, 0],
+                                            mats_dict["ida_mats"][:, 0], mats_dict.get("bda_mat", None), self.d_bound,
+                                            self.final_dim, self.downsample_factor)
+
     def forward(self, sweep_imgs, mats_dict, timestamps=None, is_return_depth=False):
         """sweep_imgs f32[B, num_sweeps, num_cams, 3, H, W] -> BEV map [B, C*num_sweeps, ny, nx]
-        (a channels-last view: the splat writes NHWC and returns its NCHW permutation)."""
+        (a channels-last view: the splat writes NHWC and returns its NCHW permutation).
+        is_return_depth: True adds the key frame's depth softmax, "logits" its raw depth logits [B*ncam, D, fH, fW]."""
         S = sweep_imgs.shape[1]
         key = self._forward_single_sweep(0, sweep_imgs[:, 0:1], mats_dict, is_return_depth)
         if S == 1:

@@ -96,22 +96,37 @@ class BEVFusionCenterHead(nn.Module):
     with_camera_encoder = property(lambda self: self.camera_encoder is not None)
     with_fusion_encoder = property(lambda self: self.fusion_encoder is not None)
 
-    def extract_bev(self, lidar_points, cameras_imgs, metas, lidar_prepared=None):
-        lidar_out = camera_out = None
+    def extract_bev(self, lidar_points, cameras_imgs, metas, lidar_prepared=None, return_depth_logits=False):
+        """return_depth_logits: -> (bev, the camera encoder's key-frame depth logits)."""
+        lidar_out = camera_out = depth_logits = None
         if self.with_lidar_encoder:
             lidar_out = self.lidar_encoder(lidar_points, lidar_prepared)
-        if self.with_camera_encoder:
+        if self.with_camera_encoder and return_depth_logits:
+            camera_out, depth_logits = self.camera_encoder(cameras_imgs, metas, is_return_depth="logits")
+        elif self.with_camera_encoder:
             camera_out = self.camera_encoder(cameras_imgs, metas)
         if self.with_fusion_encoder:
-            return self.fusion_encoder(lidar_out, camera_out)
-        return camera_out if camera_out is not None else lidar_out
+            bev = self.fusion_encoder(lidar_out, camera_out)
+        else:
+            bev = camera_out if camera_out is not None else lidar_out
+        return (bev, depth_logits) if return_depth_logits else bev
 
     def forward(self, lidar_points=None, cameras_imgs=None, metas=None, gt_boxes=None,
-                return_feature=False, targets=None, loss_norm=None, lidar_prepared=None, **_):
+                return_feature=False, targets=None, loss_norm=None, lidar_prepared=None, depth_label=None,
+                depth_weight=None, **_):
         """targets / loss_norm: optional precomputed FCOS targets and globally reduced loss
         normalisers (train.py computes them up front so the network pass holds no collective);
-        lidar_prepared: LidarEncoder.prepare(lidar_points), when the caller ran it ahead of time."""
-        bev = self.extract_bev(lidar_points, cameras_imgs, metas, lidar_prepared)
+        lidar_prepared: LidarEncoder.prepare(lidar_points), when the caller ran it ahead of time;
+        depth_label / depth_weight: LiDAR depth-bin labels i32[B, ncam, fH, fW] (LSSFPN.lidar_depth_labels) and the weight
+        of the depth loss (BEVDepth: 3.0).  With both, in training, on a model with a camera encoder,
+        depth_weight * ops.depth_sup.depth_loss joins ret['loss'] and tb['loss_depth'] holds the unweighted term."""
+        depth_sup = (depth_label is not None and depth_weight is not None and self.training and not return_feature
+                     and self.with_camera_encoder)
+        depth_logits = None
+        if depth_sup:
+            bev, depth_logits = self.extract_bev(lidar_points, cameras_imgs, metas, lidar_prepared, return_depth_logits=True)
+        else:
+            bev = self.extract_bev(lidar_points, cameras_imgs, metas, lidar_prepared)
         tapped = self.training and not return_feature
         # the two maps the box distillation losses read: their gradients join the network branch's inside one kernel (ops/distill.py)
         bev, bev_out = feature_tap(bev) if tapped else (bev, bev)
@@ -123,5 +138,10 @@ class BEVFusionCenterHead(nn.Module):
         if self.training:
             loss, tb = self.det_head.dense_head.get_loss(ret, norm=loss_norm)
             tb["loss_rpn"] = loss.detach()
+            if depth_sup:
+                from .ops.depth_sup import depth_loss
+                loss_depth = depth_loss(depth_logits, depth_label)
+                loss = loss + depth_weight * loss_depth
+                tb["loss_depth"] = loss_depth.detach()
             return {"loss": loss}, tb, bev_out, trunk_out, ret["multi_head_features"], {}
         return ret

@@ -39,12 +39,24 @@ def _tensors_in(obj):
             yield from _tensors_in(v)
 
 
+def _depth_labels(model, batch):
+    """Depth-bin labels i32[B, ncam, fH, fW] for ``model``'s camera encoder from the batch's collated LiDAR cloud."""
+    if model.camera_encoder is None:
+        raise ValueError("depth_weight is set, but the model has no camera encoder whose depth it could supervise")
+    if batch.get("points") is None or batch.get("mats_dict") is None:
+        raise ValueError("depth_weight is set, but the batch carries no LiDAR 'points' (or no 'mats_dict') to build the depth "
+                         "labels from: a camera-only batch cannot be depth-supervised")
+    return model.camera_encoder.backbone.lidar_depth_labels(batch["points"], batch["mats_dict"])[1]
+
+
 class DistillStep(nn.Module):
     """Holds the trainable student and the frozen teacher; forward(batch) returns the loss dict."""
 
     def __init__(self, experiment="camera_exp_distill_lidar", teacher_train_mode=False,
-                 student=None, teacher=None, geometry=None):
+                 student=None, teacher=None, geometry=None, depth_weight=None):
         super().__init__()
+        # LiDAR depth supervision of the student's lift (ops/depth_sup.py; BEVDepth uses 3.0): None = off, the step is unchanged
+        self.depth_weight = depth_weight
         e = dict(C.DISTILL_EXPERIMENTS[experiment]) if isinstance(experiment, str) else dict(experiment)
         self.exp = e
         # the experiment modules' _POINT_CLOUD_RANGE / _VOXEL_SIZE / _OUT_SIZE_FACTOR / _GRID_SIZE constants
@@ -97,8 +109,11 @@ class DistillStep(nn.Module):
         mask = D.calculate_box_mask_gaussian((gt.shape[0], 1, G["grid_size"][1] // osf, G["grid_size"][0] // osf),
                                              gt, pcr, vs, osf)
         local = torch.stack(head.local_normalisers(targets) + [valid.float().sum(), mask.sum()])
-        return {"gt": gt, "targets": targets, "corners": corners, "valid": valid, "mask": mask,
-                "local": local}
+        prep = {"gt": gt, "targets": targets, "corners": corners, "valid": valid, "mask": mask, "local": local}
+        if self.depth_weight is not None:
+            # on the main stream, ahead of the event the teacher's stream waits on (forward()): the cloud is read here first
+            prep["depth_label"] = _depth_labels(self.model, batch)
+        return prep
 
     @staticmethod
     def reduce(prep):
@@ -161,9 +176,10 @@ class DistillStep(nn.Module):
         e = self.exp
         norm = prep["norm"]
         nh = norm.numel() - 2
+        depth = {} if self.depth_weight is None else {"depth_label": prep["depth_label"], "depth_weight": self.depth_weight}
         ret, tb, feat_s, bev_s, resp_s, _ = self.model(
             self._points(batch), batch.get("imgs"), batch.get("mats_dict"), prep["gt"],
-            targets=prep["targets"], loss_norm=list(norm[:nh].unbind(0)))
+            targets=prep["targets"], loss_norm=list(norm[:nh].unbind(0)), **depth)
         if callable(teacher_out):                  # teacher enqueued AFTER the student forward (see forward())
             teacher_out, join = teacher_out()
         if join is not None:                       # teacher stream -> main stream hand-over
@@ -378,16 +394,20 @@ class DetectStep(nn.Module):
     """Plain (non-distill) detector training step: Exp.training_step of the base experiments
     (BEVFusion_nuscenes_base_exp.py:360-375)."""
 
-    def __init__(self, modality="lidar", model=None):
+    def __init__(self, modality="lidar", model=None, depth_weight=None):
         super().__init__()
         self.model = model if model is not None else build_model(modality)
+        self.depth_weight = depth_weight      # LiDAR depth supervision of the lift (ops/depth_sup.py); None = off
 
     def forward(self, batch):
+        depth = {}
+        if self.depth_weight is not None:
+            depth = {"depth_label": _depth_labels(self.model, batch), "depth_weight": self.depth_weight}
         points = batch.get("points")
         if points is not None and not isinstance(points, (list, tuple)):
             points = [p for p in points]
         gt = torch.cat([batch["gt_boxes"], (batch["gt_labels"] + 1).unsqueeze(2)], 2)
-        ret, tb, *_ = self.model(points, batch.get("imgs"), batch.get("mats_dict"), gt)
+        ret, tb, *_ = self.model(points, batch.get("imgs"), batch.get("mats_dict"), gt, **depth)
         return {"loss": ret["loss"].mean(), "tb": tb}
 
 

@@ -1065,6 +1065,38 @@ int ud_optim_clip_adamw_ema(const UdOptimChunk* chunks, int n_chunks, float* con
 int ud_optim_swap(const UdOptimChunk* chunks, int n_chunks, float* const* a_ptrs, float* const* b_ptrs,
                   ud_stream_t stream);
 
+/* ---- LiDAR depth supervision of the camera student's lift (csrc/depth_sup.hip) ---------------------------
+ * The BEVDepth recipe: the collated cloud is projected into the key frame's images, every feature cell keeps its
+ * MINIMUM depth, the depth net's softmax is trained against that cell's depth bin with binary cross entropy.
+ *   ud_depth_labels    points f32[B, Nmax, >= 3] (element strides stride_b, stride_n; x y z contiguous), the post-BDA
+ *                      cloud.  sensor2ego / intrin / ida f32[B, ncam, 4, 4] of the key frame, bda f32[B, 4, 4] or NULL.
+ *                      Per sample and camera, in fp64:  q = (bda . sensor2ego)^-1 . (x, y, z, 1);  (x', y', w) = upper
+ *                      3x3 of intrin . q;  (u, v, d, 1) = ida . (x' / w, y' / w, q.z, 1).  A point counts when x, y, z,
+ *                      u, v, d are finite, d_lo <= d < d_hi, 0 <= u < W, 0 <= v < H; rows with x == y == z == 0 are
+ *                      padding.  Cell (floor(v / downsample), floor(u / downsample)) keeps the minimum of (float)d.
+ *                      dmin f32[B, ncam, H / downsample, W / downsample] (+inf where empty), label i32 of that shape =
+ *                      floor((dmin - d_lo) / d_step) when inside [0, D), else -1.  Independent of the order of the
+ *                      points, bitwise reproducible.  Three launches (two when Nmax == 0).
+ *   ud_depth_loss_fwd  logits f32[BN, D, fH, fW] through element strides (sn, sc, sh, sw), D <= 256; label i32[BN, fH,
+ *                      fW].  p = softmax over D, t = onehot(label), fg = label in [0, D):
+ *                      result[0] = sum over fg pixels and bins of BCE(p, t) / max(1, |fg|) with both logs clamped at
+ *                      -100 (torch's binary_cross_entropy), result[1] = |fg|.  Ordered reduction: bitwise
+ *                      reproducible; exactly 0 without a foreground pixel.  Two launches.
+ *   ud_depth_loss_bwd  dx (strides dn, dc, dh, dw) = grad_out[0] * d result[0] / d logits, with torch's
+ *                      dBCE/dp = (p - t) / max((1 - p) p, 1e-12); exact zeros at pixels without a label.  One launch.
+ * No host synchronisation, no allocation; scratch from the caller. */
+size_t ud_depth_labels_workspace_bytes(int B, int ncam);
+int ud_depth_labels(const float* points, int64_t stride_b, int64_t stride_n, int B, int Nmax, const float* sensor2ego,
+                    const float* intrin, const float* ida, const float* bda, int ncam, int H, int W, int downsample,
+                    double d_lo, double d_hi, double d_step, int D, float* dmin, int32_t* label, void* workspace,
+                    size_t workspace_bytes, ud_stream_t stream);
+size_t ud_depth_loss_workspace_bytes(int BN, int fH, int fW);
+int ud_depth_loss_fwd(const float* logits, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const int32_t* label, int BN,
+                      int D, int fH, int fW, float* result, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+int ud_depth_loss_bwd(const float* logits, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const int32_t* label,
+                      const float* result, const float* grad_out, float* dx, int64_t dn, int64_t dc, int64_t dh,
+                      int64_t dw, int BN, int D, int fH, int fW, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
