@@ -12,9 +12,14 @@
 //           box[t][j] = sum |g_j m_j - tgt_j m_j| / (num_obj[t] + 1e-4);  axis-aligned 3-D IoU loss and the
 //           IoU-aware L1 against the nearest-BEV IoU of the (detached) decoded boxes.  The local
 //           derivatives are produced in the same pass, so the backward only scales and scatters them.
+//   reg, ROT: opt-in (ud_det_reg_*_rot).  Both IoU terms use the rotated 3-D IoU of rot_iou3d.h between the decoded
+//           prediction and target, extents paired as the assigner encoded them (3 = dx, 4 = dy, 5 = dz): the loss is
+//           sum (1 - clamp(IoU, 0, 1)) / max(num_obj, 1) with derivatives for all eight box values (yaw through
+//           atan2(sin, cos)), the IoU-aware target is 2 (IoU - 0.5) of the same number.  The box L1 is untouched.
 // Reductions are two-stage and ordered (deterministic); nothing synchronises with the host.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "rot_iou3d.h"
 
 namespace {
 
@@ -22,6 +27,7 @@ constexpr int kMaxTasks = 8;
 constexpr int kNG = 11;            // gathered values per slot: reg2 height1 dim3 rot2 vel2 iou1
 constexpr int kNB = 10;            // box code size (nuScenes)
 constexpr int kLoc = 17;           // saved local derivatives per slot: box 10, iou-loss 6, aware 1
+constexpr int kLocRot = 19;        // rotated 3-D IoU: box 10, iou-loss 8 (sin / cos too), aware 1
 constexpr int kFocalBlocks = 64;
 constexpr int kRegChunks = 8;
 
@@ -147,7 +153,8 @@ __device__ __forceinline__ void aligned_bev(float x, float y, float w, float l, 
   *x0 = x - dx / 2; *y0 = y - dy / 2; *x1 = x + dx / 2; *y1 = y + dy / 2;
 }
 
-// grid (kRegChunks, T); partial[t][chunk][nb + 2]; loc[t][b][k][kLoc]
+// grid (kRegChunks, T); partial[t][chunk][nb + 2]; loc[t][b][k][kLoc] (ROT: kLocRot)
+template <bool ROT>
 __global__ __launch_bounds__(256) void k_reg_fwd(RegArgs a, const long long* __restrict__ ind,
                                                  const unsigned char* __restrict__ mask,
                                                  const float* __restrict__ tgt, int tgt_dim,
@@ -162,11 +169,12 @@ __global__ __launch_bounds__(256) void k_reg_fwd(RegArgs a, const long long* __r
   for (int j = 0; j < kNB + 2; ++j) acc[j] = 0.f;
   for (int s = blockIdx.x * 256 + threadIdx.x; s < slots; s += gridDim.x * 256) {
     const size_t so = (size_t)t * slots + s;
-    float* L = loc + so * kLoc;
+    constexpr int kL = ROT ? kLocRot : kLoc;
+    float* L = loc + so * kL;
     const bool m = mask[so] != 0;
     if (!m) {
 #pragma unroll
-      for (int j = 0; j < kLoc; ++j) L[j] = 0.f;
+      for (int j = 0; j < kL; ++j) L[j] = 0.f;
       continue;
     }
     const int b = s / a.K;
@@ -194,6 +202,29 @@ __global__ __launch_bounds__(256) void k_reg_fwd(RegArgs a, const long long* __r
     }
     const float px = g[0] * a.sx, py = g[1] * a.sy, pz = g[2];
     const float tx = tg[0] * a.sx, ty = tg[1] * a.sy, tz = tg[2];
+    if constexpr (ROT) {
+      // rotated 3-D IoU of the decoded boxes, once: loss term, its 8 derivatives, and the IoU-aware target
+      const float sn = g[6], cs = g[7], r2 = sn * sn + cs * cs;
+      const float pb[7] = {px, py, pz, pw[0], pw[1], pw[2], atan2f(sn, cs)};
+      const float tb[7] = {tx, ty, tz, tw[0], tw[1], tw[2], atan2f(tg[6], tg[7])};
+      float di[7];
+      const float iou = ud_riou::iou3d<true>(pb, tb, di);
+      acc[kNB] += iou != iou ? iou : 1.f - fminf(fmaxf(iou, 0.f), 1.f);          // a NaN propagates like the box terms
+      const float dL = (iou >= 0.f && iou <= 1.f) ? -1.f / den_iou : 0.f;          // d loss / d iou
+      // chain to the head values: centre scale, exp of the extents (a clamped one passes 0), yaw = atan2(sin, cos)
+      const float ch[8] = {a.sx, a.sy, 1.f, dpw[0], dpw[1], dpw[2], r2 > 0.f ? cs / r2 : 0.f, r2 > 0.f ? -sn / r2 : 0.f};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = dL * di[j < 6 ? j : 6] * ch[j];
+        L[kNB + j] = fabsf(v) <= 3.4e38f ? v : 0.f;                                // never hand a NaN / inf to the optimizer
+      }
+      const float tar = 2.f * (iou - 0.5f);
+      const float ma = isnan(tar) ? 0.f : 1.f;
+      const float da = g[kNG - 1] * ma - tar * ma;
+      acc[kNB + 1] += fabsf(da);
+      L[kNB + 8] = sgn(da) * ma / den_box;
+      continue;
+    }
     float dxc, dxe, dyc, dye, dzc, dze;
     const float ox = overlap(px, pw[0], tx, tw[0], &dxc, &dxe);
     const float oy = overlap(py, pw[2], ty, tw[2], &dyc, &dye);
@@ -246,6 +277,7 @@ __global__ __launch_bounds__(256) void k_reg_fwd(RegArgs a, const long long* __r
 }
 
 // dhead[t][b][j][pix] = g_box[t][j] * L_box[j] + g_iou[t] * L_iou[j] (+ g_aw[t] * L_aw for the iou head)
+template <bool ROT>
 __global__ __launch_bounds__(256) void k_reg_bwd(RegArgs a, const long long* __restrict__ ind,
                                                  const unsigned char* __restrict__ mask,
                                                  const float* __restrict__ loc,
@@ -257,18 +289,80 @@ __global__ __launch_bounds__(256) void k_reg_bwd(RegArgs a, const long long* __r
   for (long long so = (long long)blockIdx.x * 256 + threadIdx.x; so < total; so += (long long)gridDim.x * 256) {
     if (!mask[so]) continue;
     const int t = (int)(so / slots), s = (int)(so - (long long)t * slots), b = s / a.K;
-    const float* L = loc + so * kLoc;
+    constexpr int kIou = ROT ? 8 : 6;           // values the IoU loss reaches
+    const float* L = loc + so * (ROT ? kLocRot : kLoc);
     const long long pix = ind[so];
     float* dst = dhead + (((size_t)t * a.B + b) * kNG) * a.HW + pix;
 #pragma unroll
     for (int j = 0; j < kNG; ++j) {
       float v = 0.f;
       if (j < a.nb) v += g_box[t * kNB + j] * L[j];
-      if (j < 6) v += g_iou[t] * L[kNB + j];
-      if (j == kNG - 1) v = g_aw[t] * L[kNB + 6];
+      if (j < kIou) v += g_iou[t] * L[kNB + j];
+      if (j == kNG - 1) v = g_aw[t] * L[kNB + kIou];
       if (j < a.nb || j == kNG - 1) dst[(size_t)j * a.HW] = v;
     }
   }
+}
+
+// iou[i] = IoU3D_rot(a[i], b[i]); diou[i][0..7) = d iou[i] / d a[i] (optional)
+__global__ __launch_bounds__(256) void k_rot_iou3d_pairs(const float* __restrict__ a, const float* __restrict__ b, int N,
+                                                         float* __restrict__ iou, float* __restrict__ diou) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  float pa[7], pb[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) { pa[j] = a[(size_t)i * 7 + j]; pb[j] = b[(size_t)i * 7 + j]; }
+  if (diou) {
+    float d[7];
+    iou[i] = ud_riou::iou3d<true>(pa, pb, d);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) diou[(size_t)i * 7 + j] = d[j];
+  } else {
+    iou[i] = ud_riou::iou3d<false>(pa, pb, nullptr);
+  }
+}
+
+template <bool ROT>
+int reg_fwd(const float* const* head, const long long* head_bstride, int T, int B, int K, int HW, int nb,
+            const long long* ind, const unsigned char* mask, const float* tgt, int tgt_dim, const float* num_obj,
+            float sx, float sy, float* losses, float* loc, void* workspace, size_t workspace_bytes,
+            ud_stream_t stream_) {
+  if (!head || !head_bstride || !ind || !mask || !tgt || !num_obj || !losses || !loc || T <= 0 ||
+      T > kMaxTasks || B <= 0 || K <= 0 || HW <= 0 || (nb != 10 && nb != 8) || tgt_dim < nb)
+    return UD_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < ud_det_loss_workspace_bytes(T)) return UD_ERR_WORKSPACE;
+  RegArgs a;
+  for (int t = 0; t < T; ++t)
+    for (int j = 0; j < kNG; ++j) {
+      a.head[t][j] = head[t * kNG + j];
+      a.bstride[t][j] = head_bstride[t * kNG + j];
+      if ((j < nb || j == kNG - 1) && !a.head[t][j]) return UD_ERR_INVALID_ARG;
+    }
+  a.T = T; a.B = B; a.K = K; a.HW = HW; a.nb = nb; a.sx = sx; a.sy = sy;
+  hipStream_t stream = (hipStream_t)stream_;
+  float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) +
+                                            ud_align_up((size_t)T * kFocalBlocks * 2 * sizeof(float)));
+  UdProfScope prof(ROT ? "det_loss.reg_fwd_rot" : "det_loss.reg_fwd", stream);
+  k_reg_fwd<ROT><<<dim3(kRegChunks, T), 256, 0, stream>>>(a, ind, mask, tgt, tgt_dim, num_obj, partial, loc);
+  UD_LAUNCH_CHECK();
+  // partial rows are kNB + 2 wide; the caller's losses rows are nb + 2 wide
+  k_sum_partials<<<1, 128, 0, stream>>>(partial, kRegChunks, kNB + 2, T * (kNB + 2), losses);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
+}
+
+template <bool ROT>
+int reg_bwd(int T, int B, int K, int HW, int nb, const long long* ind, const unsigned char* mask, const float* loc,
+            const float* g_box, const float* g_iou, const float* g_aw, float* dhead, ud_stream_t stream_) {
+  if (!ind || !mask || !loc || !g_box || !g_iou || !g_aw || !dhead || T <= 0 || T > kMaxTasks || B <= 0 ||
+      K <= 0 || HW <= 0 || (nb != 10 && nb != 8))
+    return UD_ERR_INVALID_ARG;
+  RegArgs a;
+  a.T = T; a.B = B; a.K = K; a.HW = HW; a.nb = nb; a.sx = a.sy = 0.f;
+  const long long total = (long long)T * B * K;
+  k_reg_bwd<ROT><<<ud_div_up(total, 256), 256, 0, (hipStream_t)stream_>>>(a, ind, mask, loc, g_box, g_iou, g_aw, dhead);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
 }
 
 }  // namespace
@@ -332,41 +426,38 @@ int ud_det_reg_fwd(const float* const* head, const long long* head_bstride, int 
                    int nb, const long long* ind, const unsigned char* mask, const float* tgt, int tgt_dim,
                    const float* num_obj, float sx, float sy, float* losses, float* loc, void* workspace,
                    size_t workspace_bytes, ud_stream_t stream_) {
-  if (!head || !head_bstride || !ind || !mask || !tgt || !num_obj || !losses || !loc || T <= 0 ||
-      T > kMaxTasks || B <= 0 || K <= 0 || HW <= 0 || (nb != 10 && nb != 8) || tgt_dim < nb)
-    return UD_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < ud_det_loss_workspace_bytes(T)) return UD_ERR_WORKSPACE;
-  RegArgs a;
-  for (int t = 0; t < T; ++t)
-    for (int j = 0; j < kNG; ++j) {
-      a.head[t][j] = head[t * kNG + j];
-      a.bstride[t][j] = head_bstride[t * kNG + j];
-      if ((j < nb || j == kNG - 1) && !a.head[t][j]) return UD_ERR_INVALID_ARG;
-    }
-  a.T = T; a.B = B; a.K = K; a.HW = HW; a.nb = nb; a.sx = sx; a.sy = sy;
-  hipStream_t stream = (hipStream_t)stream_;
-  float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) +
-                                            ud_align_up((size_t)T * kFocalBlocks * 2 * sizeof(float)));
-  UdProfScope prof("det_loss.reg_fwd", stream);
-  k_reg_fwd<<<dim3(kRegChunks, T), 256, 0, stream>>>(a, ind, mask, tgt, tgt_dim, num_obj, partial, loc);
-  UD_LAUNCH_CHECK();
-  // partial rows are kNB + 2 wide; the caller's losses rows are nb + 2 wide
-  k_sum_partials<<<1, 128, 0, stream>>>(partial, kRegChunks, kNB + 2, T * (kNB + 2), losses);
-  UD_LAUNCH_CHECK();
-  return UD_OK;
+  return reg_fwd<false>(head, head_bstride, T, B, K, HW, nb, ind, mask, tgt, tgt_dim, num_obj, sx, sy, losses, loc,
+                        workspace, workspace_bytes, stream_);
 }
 
 // dhead: [T, B, 11, HW] fp32, zero-initialised by the caller; g_box [T, 10], g_iou [T], g_aw [T] device.
 int ud_det_reg_bwd(int T, int B, int K, int HW, int nb, const long long* ind, const unsigned char* mask,
                    const float* loc, const float* g_box, const float* g_iou, const float* g_aw,
                    float* dhead, ud_stream_t stream_) {
-  if (!ind || !mask || !loc || !g_box || !g_iou || !g_aw || !dhead || T <= 0 || T > kMaxTasks || B <= 0 ||
-      K <= 0 || HW <= 0 || (nb != 10 && nb != 8))
-    return UD_ERR_INVALID_ARG;
-  RegArgs a;
-  a.T = T; a.B = B; a.K = K; a.HW = HW; a.nb = nb; a.sx = a.sy = 0.f;
-  const long long total = (long long)T * B * K;
-  k_reg_bwd<<<ud_div_up(total, 256), 256, 0, (hipStream_t)stream_>>>(a, ind, mask, loc, g_box, g_iou, g_aw, dhead);
+  return reg_bwd<false>(T, B, K, HW, nb, ind, mask, loc, g_box, g_iou, g_aw, dhead, stream_);
+}
+
+// The same pair with the rotated 3-D IoU (rot_iou3d.h) in both IoU terms; loc: [T, B, K, 19].
+int ud_det_reg_fwd_rot(const float* const* head, const long long* head_bstride, int T, int B, int K, int HW,
+                       int nb, const long long* ind, const unsigned char* mask, const float* tgt, int tgt_dim,
+                       const float* num_obj, float sx, float sy, float* losses, float* loc, void* workspace,
+                       size_t workspace_bytes, ud_stream_t stream_) {
+  return reg_fwd<true>(head, head_bstride, T, B, K, HW, nb, ind, mask, tgt, tgt_dim, num_obj, sx, sy, losses, loc,
+                       workspace, workspace_bytes, stream_);
+}
+
+int ud_det_reg_bwd_rot(int T, int B, int K, int HW, int nb, const long long* ind, const unsigned char* mask,
+                       const float* loc, const float* g_box, const float* g_iou, const float* g_aw,
+                       float* dhead, ud_stream_t stream_) {
+  return reg_bwd<true>(T, B, K, HW, nb, ind, mask, loc, g_box, g_iou, g_aw, dhead, stream_);
+}
+
+// a, b: [N, 7] boxes (x, y, z, dx, dy, dz, yaw); iou: [N]; diou_da: [N, 7] or NULL.
+int ud_rot_iou3d_pairs(const float* a, const float* b, int N, float* iou, float* diou_da, ud_stream_t stream_) {
+  if (N < 0) return UD_ERR_INVALID_ARG;
+  if (N == 0) return UD_OK;
+  if (!a || !b || !iou) return UD_ERR_INVALID_ARG;
+  k_rot_iou3d_pairs<<<ud_div_up(N, 256), 256, 0, (hipStream_t)stream_>>>(a, b, N, iou, diou_da);
   UD_LAUNCH_CHECK();
   return UD_OK;
 }

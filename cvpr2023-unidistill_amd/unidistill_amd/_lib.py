@@ -174,6 +174,11 @@ _SIGS = {
                                                                      c_void_p, c_float, c_float, c_void_p,
                                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "ud_det_reg_bwd": (c_int, [c_int] * 5 + [c_void_p] * 8),
+    "ud_det_reg_fwd_rot": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int,
+                                                                         c_void_p, c_float, c_float, c_void_p,
+                                                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ud_det_reg_bwd_rot": (c_int, [c_int] * 5 + [c_void_p] * 8),
+    "ud_rot_iou3d_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ud_nms_bev_workspace_bytes": (c_size_t, [c_int]),
     "ud_nms_rotated_bev": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ud_boxes_iou_bev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),

@@ -61,10 +61,13 @@ DET_HEAD = dict(
                   nms_iou_threshold_test=0.1, nms_pre_max_size_test=1500, nms_post_max_size_test=100))
 
 
-def model_cfg(lidar=True, camera=True):
+def model_cfg(lidar=True, camera=True, iou_mode=None):
+    """iou_mode: None / "reference" = the reference's IoU terms; "rotated3d" = the rotated 3-D IoU in the head's loss."""
     cfg = dict(class_names=CLASS_NAMES, lidar_encoder=copy.deepcopy(LIDAR_ENCODER) if lidar else None,
                camera_encoder=copy.deepcopy(CAMERA_ENCODER) if camera else None,
                bev_encoder=copy.deepcopy(BEV_ENCODER), det_head=copy.deepcopy(DET_HEAD))
+    if iou_mode is not None:
+        cfg["det_head"]["iou_mode"] = iou_mode
     return cfg
 
 

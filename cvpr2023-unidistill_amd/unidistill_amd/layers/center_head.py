@@ -668,7 +668,7 @@ class CenterHeadIouAware(CenterHead):
                  input_channels, grid_size, point_cloud_range, code_weights, loc_weight, iou_weight,
                  share_conv_channel, common_heads, upsample_for_pedestrian=False,
                  predict_boxes_when_training=False, mode="3d", init_bias=-2.19,
-                 focal_alpha=0.25, focal_gamma=2, voxel_size_xy=None, packed_heads=True):
+                 focal_alpha=0.25, focal_gamma=2, voxel_size_xy=None, packed_heads=True, iou_mode="reference"):
         super().__init__(dataset_name, tasks, target_assigner, proposal_layer, input_channels,
                          grid_size, point_cloud_range, code_weights, loc_weight, share_conv_channel,
                          common_heads, upsample_for_pedestrian, predict_boxes_when_training, mode,
@@ -681,6 +681,12 @@ class CenterHeadIouAware(CenterHead):
         self.crit_reg = CenterNetRegLoss()
         self.crit_iou_aware = CenterNetRegLoss()
         self._voxel_size_xy = voxel_size_xy
+        self.set_iou_mode(iou_mode)
+
+    def set_iou_mode(self, iou_mode):
+        """"reference": the reference's axis-aligned IoU loss and nearest-BEV IoU-aware target (default).  "rotated3d": both from
+        the rotated 3-D IoU of the decoded boxes, yaw included (ops/det_loss.py); HIP path only."""
+        self.iou_mode = hiploss.check_iou_mode(iou_mode)
 
     def _code_weights(self, like):
         cw = getattr(self, "_cw_cache", None)
@@ -735,13 +741,17 @@ class CenterHeadIouAware(CenterHead):
             heads, nb = ("reg", "height", "dim", "rot", "iou"), 8
         a, gm = self.crit.alpha, self.crit.gamma
         stride, vs = self.out_size_factor, self._voxel_xy()
+        if self.iou_mode == "rotated3d" and not (self.fused_loss and hiploss.supported(preds, nb)):
+            some = preds[0]["hm"]
+            raise ValueError(f'iou_mode="rotated3d" runs on the HIP detection-loss kernels only (fp32 GPU head tensors with '
+                             f"contiguous planes, nuScenes box code, fused_loss on); got heads on {some.device} in {some.dtype}")
         if self.fused_loss and hiploss.supported(preds, nb):
             # ---- HIP path: focal term over all heat maps + gathered regression / IoU terms, 2 kernels
             prob, pos_l, neg_l = hiploss.focal_terms([pd["hm"] for pd in preds], gt_hm, a, gm)
             for t, pd in enumerate(preds):
                 pd["hm"] = prob[t, :, :self.num_classes[t]]
             box_loss, iou_loss, iou_aware = hiploss.reg_terms(preds, ind, mask, tgt_all, num_obj,
-                                                              stride * vs[0], stride * vs[1], nb)
+                                                              stride * vs[0], stride * vs[1], nb, self.iou_mode)
         else:
             pos_l, neg_l, box_loss, iou_loss, iou_aware = self._loss_terms_torch(
                 preds, gt_hm, ind, mask, tgt_all, num_obj, ncm, heads, nb, a, gm, stride, vs, forward_ret_dict)

@@ -59,7 +59,7 @@ class DetHead(nn.Module):
             code_weights=cfg["code_weights"], loc_weight=cfg["loc_weight"], iou_weight=cfg["iou_weight"],
             share_conv_channel=cfg["share_conv_channel"], common_heads=cfg["common_heads"],
             init_bias=cfg["init_bias"], focal_alpha=cfg["focal_alpha"], focal_gamma=cfg["focal_gamma"],
-            voxel_size_xy=cfg["voxel_size"][0:2])
+            voxel_size_xy=cfg["voxel_size"][0:2], iou_mode=cfg.get("iou_mode", "reference"))
 
     def forward(self, x, gt_boxes, targets=None):
         ret = self.dense_head(x, gt_boxes, targets=targets)

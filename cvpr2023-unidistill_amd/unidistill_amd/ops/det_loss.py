@@ -4,6 +4,9 @@ CenterHeadIouAware.get_loss (reference layers/head/det3d/center_head_iou_aware.p
 CenterNetRegLoss of layers/losses/det3d.py:287-421) evaluates ~330 small tensor ops per step; here the
 focal term over all heat maps and the gathered regression / IoU terms are one forward kernel each, with
 the local derivatives kept for a scale-and-scatter backward.
+
+``iou_mode="rotated3d"`` (opt-in) replaces the reference's axis-aligned IoU loss and nearest-BEV IoU-aware target by the
+rotated 3-D IoU of the decoded boxes (ud_det_reg_*_rot); ``rotated_iou3d`` is that IoU as a pairwise op on plain boxes.
 """
 import ctypes
 
@@ -13,6 +16,13 @@ from .. import _lib
 
 HEADS = ("reg", "height", "dim", "rot", "vel", "iou")       # gathered order: 2+1+3+2+2+1 = 11 values
 WIDTH = (2, 1, 3, 2, 2, 1)
+IOU_MODES = ("reference", "rotated3d")
+
+
+def check_iou_mode(iou_mode):
+    if iou_mode not in IOU_MODES:
+        raise ValueError(f"iou_mode must be one of {IOU_MODES}, got {iou_mode!r}")
+    return iou_mode
 
 
 def supported(preds, nb):
@@ -73,6 +83,8 @@ def focal_terms(hms, gt, alpha, gamma):
 
 
 class _RegFn(torch.autograd.Function):
+    FWD, BWD, LOC = "ud_det_reg_fwd", "ud_det_reg_bwd", 17      # entry points and saved derivatives per slot
+
     @staticmethod
     def forward(ctx, ind, mask, tgt, num_obj, sx, sy, nb, *heads):
         """heads: T * 6 tensors in HEADS order per task."""
@@ -94,12 +106,13 @@ class _RegFn(torch.autograd.Function):
         num_obj = num_obj.contiguous().float()
         dev = ind.device
         losses = torch.empty((T, 12), dtype=torch.float32, device=dev)
-        loc = torch.empty((T, B, K, 17), dtype=torch.float32, device=dev)
+        loc = torch.empty((T, B, K, ctx._forward_cls.LOC), dtype=torch.float32, device=dev)
         ws = _lib.workspace(dev, lib.ud_det_loss_workspace_bytes(T), "det_loss")
-        _lib.check(lib.ud_det_reg_fwd(table, (ctypes.c_longlong * len(strides))(*strides), T, B, K, H * W, nb,
-                                      _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(tgt), tgt.shape[-1],
-                                      _lib.ptr(num_obj), float(sx), float(sy), _lib.ptr(losses), _lib.ptr(loc),
-                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(ind)), "ud_det_reg_fwd")
+        fwd = ctx._forward_cls.FWD
+        _lib.check(getattr(lib, fwd)(table, (ctypes.c_longlong * len(strides))(*strides), T, B, K, H * W, nb,
+                                     _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(tgt), tgt.shape[-1],
+                                     _lib.ptr(num_obj), float(sx), float(sy), _lib.ptr(losses), _lib.ptr(loc),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_of(ind)), fwd)
         ctx.save_for_backward(ind, mask_u8, loc)
         ctx.cfg = (T, B, K, H, W, nb)
         return losses[:, :10], losses[:, 10], losses[:, 11]
@@ -110,10 +123,10 @@ class _RegFn(torch.autograd.Function):
         T, B, K, H, W, nb = ctx.cfg
         dhead = torch.zeros((T, B, 11, H, W), dtype=torch.float32, device=ind.device)
         z = lambda g, shape: (torch.zeros(shape, device=ind.device) if g is None else g.contiguous().float())
-        _lib.check(_lib.load().ud_det_reg_bwd(T, B, K, H * W, nb, _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(loc),
-                                              _lib.ptr(z(g_box, (T, 10))), _lib.ptr(z(g_iou, (T,))),
-                                              _lib.ptr(z(g_aw, (T,))), _lib.ptr(dhead), _lib.stream_of(ind)),
-                   "ud_det_reg_bwd")
+        bwd = ctx._forward_cls.BWD
+        _lib.check(getattr(_lib.load(), bwd)(T, B, K, H * W, nb, _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(loc),
+                                             _lib.ptr(z(g_box, (T, 10))), _lib.ptr(z(g_iou, (T,))),
+                                             _lib.ptr(z(g_aw, (T,))), _lib.ptr(dhead), _lib.stream_of(ind)), bwd)
         grads = []
         for t in range(T):
             c = 0
@@ -123,8 +136,48 @@ class _RegFn(torch.autograd.Function):
         return (None,) * 7 + tuple(grads)
 
 
-def reg_terms(preds, ind, mask, tgt, num_obj, sx, sy, nb=10):
+class _RegRotFn(_RegFn):
+    """The same terms with the rotated 3-D IoU (ud_det_reg_*_rot): 19 saved derivatives per slot, gradients reach rot too."""
+    FWD, BWD, LOC = "ud_det_reg_fwd_rot", "ud_det_reg_bwd_rot", 19
+
+
+def reg_terms(preds, ind, mask, tgt, num_obj, sx, sy, nb=10, iou_mode="reference"):
     """preds: per-task dicts of head tensors; ind/mask [T,B,K], tgt [T,B,K,>=nb], num_obj [T]
-    -> (box_loss [T,10], iou_loss [T], iou_aware [T]) normalised like the reference."""
+    -> (box_loss [T,10], iou_loss [T], iou_aware [T]) normalised like the reference.
+    iou_mode "reference": the reference's axis-aligned IoU loss and nearest-BEV IoU-aware target; "rotated3d": both from the
+    rotated 3-D IoU of the decoded prediction and target (box_loss is the same either way).  Gradients go to the heads only."""
     heads = [pd[name] for pd in preds for name in HEADS]
-    return _RegFn.apply(ind, mask, tgt, num_obj, sx, sy, nb, *heads)
+    fn = _RegFn
+    if check_iou_mode(iou_mode) == "rotated3d":
+        _lib.require_gpu(ind, *heads)
+        fn = _RegRotFn
+    return fn.apply(ind, mask, tgt, num_obj, sx, sy, nb, *heads)
+
+
+class _RotIou3dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        n = a.shape[0]
+        iou = torch.empty((n,), dtype=torch.float32, device=a.device)
+        diou = torch.empty((n, 7), dtype=torch.float32, device=a.device) if ctx.needs_input_grad[0] else None
+        _lib.check(_lib.load().ud_rot_iou3d_pairs(_lib.ptr(a), _lib.ptr(b), n, _lib.ptr(iou), _lib.ptr(diou),
+                                                  _lib.stream_of(a)), "ud_rot_iou3d_pairs")
+        if diou is not None:
+            ctx.save_for_backward(diou)
+        return iou
+
+    @staticmethod
+    def backward(ctx, g):
+        diou, = ctx.saved_tensors
+        return g[:, None] * diou, None
+
+
+def rotated_iou3d(a, b):
+    """a, b: fp32 GPU boxes [N,7] (x, y, z, dx, dy, dz, yaw) -> IoU3D_rot(a[i], b[i]) [N]: area of the intersection of the
+    two rotated rectangles x z-overlap, over the union (floor 1e-8).  Differentiable in a; b is a constant."""
+    _lib.require_gpu(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise TypeError(f"rotated_iou3d takes float32 boxes, got {a.dtype} and {b.dtype}")
+    if a.dim() != 2 or a.shape[1] != 7 or a.shape != b.shape:
+        raise ValueError(f"rotated_iou3d takes two [N, 7] box tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return _RotIou3dFn.apply(a.contiguous(), b.detach().contiguous())

@@ -21,10 +21,16 @@ from .models import BEVFusionCenterHead
 from .ops import distill as D, wgrad_stream
 
 
-def build_model(modality, **kw):
+def build_model(modality, iou_mode=None, **kw):
     """modality: 'camera' | 'lidar' | 'fusion' -> BEVFusionCenterHead."""
-    cfg = C.model_cfg(lidar=modality in ("lidar", "fusion"), camera=modality in ("camera", "fusion"))
+    cfg = C.model_cfg(lidar=modality in ("lidar", "fusion"), camera=modality in ("camera", "fusion"), iou_mode=iou_mode)
     return BEVFusionCenterHead(cfg, **kw)
+
+
+def _set_iou_mode(model, iou_mode):
+    """IoU terms of the trained model's detection loss (layers/center_head.py); None leaves the head as it was built."""
+    if iou_mode is not None:
+        model.det_head.dense_head.set_iou_mode(iou_mode)
 
 
 def _tensors_in(obj):
@@ -53,7 +59,7 @@ class DistillStep(nn.Module):
     """Holds the trainable student and the frozen teacher; forward(batch) returns the loss dict."""
 
     def __init__(self, experiment="camera_exp_distill_lidar", teacher_train_mode=False,
-                 student=None, teacher=None, geometry=None, depth_weight=None):
+                 student=None, teacher=None, geometry=None, depth_weight=None, iou_mode=None):
         super().__init__()
         # LiDAR depth supervision of the student's lift (ops/depth_sup.py; BEVDepth uses 3.0): None = off, the step is unchanged
         self.depth_weight = depth_weight
@@ -66,6 +72,7 @@ class DistillStep(nn.Module):
         geo.update(geometry or {})
         self.geo = geo
         self.model = student if student is not None else build_model(e["student"])
+        _set_iou_mode(self.model, iou_mode)        # the student's head only: the teacher's head runs no loss
         self.teacher_model = teacher if teacher is not None else build_model(e["teacher"])
         self.teacher_model.det_head.dense_head.distill = True
         for p in self.teacher_model.parameters():
@@ -394,9 +401,10 @@ class DetectStep(nn.Module):
     """Plain (non-distill) detector training step: Exp.training_step of the base experiments
     (BEVFusion_nuscenes_base_exp.py:360-375)."""
 
-    def __init__(self, modality="lidar", model=None, depth_weight=None):
+    def __init__(self, modality="lidar", model=None, depth_weight=None, iou_mode=None):
         super().__init__()
         self.model = model if model is not None else build_model(modality)
+        _set_iou_mode(self.model, iou_mode)
         self.depth_weight = depth_weight      # LiDAR depth supervision of the lift (ops/depth_sup.py); None = off
 
     def forward(self, batch):

@@ -915,6 +915,12 @@ int ud_proposal_layer(const float* const* heads, const long long* strides, const
  *                      losses [T,12] = box L1 per code dim (10), IoU loss, IoU-aware L1, all normalised;
  *                      loc [T,B,K,17] = local derivatives kept for the backward.  nb = 10 (nuScenes codes).
  *   ud_det_reg_bwd   : dhead [T,B,11,HW] (caller zero-fills) += scaled local derivatives at the slots.
+ *   ud_det_reg_fwd_rot / ud_det_reg_bwd_rot : the same pair (same arguments, same box L1) with the rotated 3-D IoU
+ *                       of the decoded prediction and target in both IoU terms: IoU loss
+ *                      sum (1 - clamp(IoU,0,1)) / max(num_obj,1) with derivatives for reg, height, dim AND rot, IoU-aware
+ *                      target 2 (IoU - 0.5).  loc [T,B,K,19] (10 box, 8 IoU-loss, 1 aware).
+ *   ud_rot_iou3d_pairs : iou [N] = IoU3D_rot(a[i], b[i]) of boxes [N,7] = x y z dx dy dz yaw (rotated-rectangle
+ *                      intersection x z-overlap over the union, floor 1e-8); diou_da [N,7] = d iou[i] / d a[i], or NULL.
  * Ordered two-stage reductions; no host synchronisation. */
 size_t ud_det_loss_workspace_bytes(int T);
 int ud_det_focal_fwd(const float* const* hm, const long long* hm_bstride, const int* ncls, int T, int B,
@@ -930,6 +936,14 @@ int ud_det_reg_fwd(const float* const* head, const long long* head_bstride, int 
 int ud_det_reg_bwd(int T, int B, int K, int HW, int nb, const long long* ind, const unsigned char* mask,
                    const float* loc, const float* g_box, const float* g_iou, const float* g_aw,
                    float* dhead, ud_stream_t stream);
+int ud_det_reg_fwd_rot(const float* const* head, const long long* head_bstride, int T, int B, int K, int HW,
+                       int nb, const long long* ind, const unsigned char* mask, const float* tgt, int tgt_dim,
+                       const float* num_obj, float sx, float sy, float* losses, float* loc, void* workspace,
+                       size_t workspace_bytes, ud_stream_t stream);
+int ud_det_reg_bwd_rot(int T, int B, int K, int HW, int nb, const long long* ind, const unsigned char* mask,
+                       const float* loc, const float* g_box, const float* g_iou, const float* g_aw,
+                       float* dhead, ud_stream_t stream);
+int ud_rot_iou3d_pairs(const float* a, const float* b, int N, float* iou, float* diou_da, ud_stream_t stream);
 
 /* ---- FCOS-style target assignment of the CenterPoint heads -----------------------------------
  * FCOSAssigner.assign_targets (reference layers/head/det3d/target_assigner/fcos_assigner.py:73-285) for all

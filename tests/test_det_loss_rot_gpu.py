@@ -1,0 +1,295 @@
+"""GPU: the detection loss's gathered terms in iou_mode="rotated3d" (ud_det_reg_fwd_rot / ud_det_reg_bwd_rot) at the smallest shapes
+that still exercise them, against the float64 restatement of tests/rot_iou_reference.py composed with the same head decode.
+
+Tolerances follow tests/test_rot_iou_gpu.py: 4x what a float32 evaluation of the restatement loses against its float64 one on these
+inputs, never below 1e-6; gradients are compared at the slots at least rot_iou_reference.MARGIN away from every decision."""
+import functools
+import math
+
+import pytest
+import torch
+
+import rot_iou_reference as R
+
+pytestmark = pytest.mark.gpu
+
+T, B, K, H, W = 2, 2, 16, 8, 8
+SX, SY = 0.6, 0.8
+WIDTH = (2, 1, 3, 2, 2, 1)          # reg height dim rot vel iou
+NAMES = ("reg", "height", "dim", "rot", "vel", "iou")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(nb, scenario):
+    """-> dict of CPU tensors: planes f32 [T,B,11,HW], ind, mask, tgt f32 [T,B,K,10], num_obj, weights, and the float64 / float32
+    restatement's losses and gradients by the gathered values."""
+    g = torch.Generator().manual_seed(11 + nb)
+    n = T * B * K
+    pred, tcode = R.random_codes(n, SX, SY, seed=5)
+    u = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)
+    code = torch.cat([pred, u(n, 2) * 2 - 1, u(n, 1) * 2 - 1], 1).reshape(T, B, K, 11)          # + vel, iou head
+    tgt = torch.cat([tcode, u(n, 2) * 2 - 1], 1).reshape(T, B, K, 10)
+    ind = torch.stack([torch.randperm(H * W, generator=g)[:K] for _ in range(T * B)]).reshape(T, B, K)   # unique per (task, sample)
+    mask = torch.rand(T, B, K, generator=g) < 0.5
+    if scenario == "empty_task":
+        mask[1] = False
+    mask[0, 0, 0] = mask[0, 1, 3] = True
+    tgt[0, 1, 3, 8] = float("nan")                       # a NaN velocity target, as nuScenes has them
+    planes = (torch.randn(T, B, 11, H * W, generator=g, dtype=torch.float64) * 0.3)
+    planes.scatter_(3, ind[:, :, None, :].expand(T, B, 11, K), code.permute(0, 1, 3, 2))
+    planes, tgt = planes.float(), tgt.float()
+    num_obj = mask.float().sum(dim=(1, 2))
+    w_box, w_iou, w_aw = 0.5 + u(T, 10), 0.5 + u(T), 0.5 + u(T)
+    out = dict(planes=planes, ind=ind, mask=mask, tgt=tgt, num_obj=num_obj, w=(w_box, w_iou, w_aw))
+    for name, dt in (("f64", torch.float64), ("f32", torch.float32)):
+        gath = planes.to(dt).gather(3, ind[:, :, None, :].expand(T, B, 11, K)).permute(0, 1, 3, 2).clone().requires_grad_(True)
+        box, il, aw, margin = R.reg_terms_ref(gath, tgt.to(dt), mask, num_obj, SX, SY, nb)
+        total = (box * w_box[:, :nb].to(dt)).sum() + (il * w_iou.to(dt)).sum() + (aw * w_aw.to(dt)).sum()
+        grad, = torch.autograd.grad(total, gath)
+        out[name] = (il.detach().double(), aw.detach().double(), grad.double(), margin)
+    return out
+
+
+def _preds(planes, packed):
+    """Head tensors [B, c, H, W] per task from planes [T,B,11,HW]: separate contiguous leaves, or channel slices of ONE packed leaf with
+    a spare channel between the heads (what PackedSepHeads returns).  -> (preds, leaves)."""
+    preds, leaves = [], []
+    if packed:
+        pk = torch.zeros(B, T * 11 + T * 6, H, W, device="cuda")
+        c = 0
+        slots = []
+        for t in range(T):
+            j = 0
+            for wd in WIDTH:
+                pk[:, c:c + wd] = planes[t, :, j:j + wd].reshape(B, wd, H, W).cuda()
+                slots.append((c, wd))
+                c += wd + 1
+                j += wd
+        pk.requires_grad_(True)
+        leaves.append(pk)
+        it = iter(slots)
+        for t in range(T):
+            preds.append({nm: pk[:, c0:c0 + wd] for nm, (c0, wd) in zip(NAMES, (next(it) for _ in NAMES))})
+        return preds, leaves, slots
+    for t in range(T):
+        pd, j = {}, 0
+        for nm, wd in zip(NAMES, WIDTH):
+            pd[nm] = planes[t, :, j:j + wd].reshape(B, wd, H, W).cuda().contiguous().requires_grad_(True)
+            leaves.append(pd[nm])
+            j += wd
+        preds.append(pd)
+    return preds, leaves, None
+
+
+def _plane_grads(leaves, slots, packed):
+    """-> [T,B,11,HW] gradient planes on the CPU (zeros where a head got none)."""
+    out = torch.zeros(T, B, 11, H * W)
+    if packed:
+        gr = leaves[0].grad.cpu()
+        it = iter(slots)
+        for t in range(T):
+            j = 0
+            for wd in WIDTH:
+                c0, _ = next(it)
+                out[t, :, j:j + wd] = gr[:, c0:c0 + wd].reshape(B, wd, H * W)
+                j += wd
+        used = torch.zeros(gr.shape[1], dtype=torch.bool)
+        for c0, wd in slots:
+            used[c0:c0 + wd] = True
+        assert float(gr[:, ~used].abs().max()) == 0.0          # the spare channels between the heads stay untouched
+        return out
+    it = iter(leaves)
+    for t in range(T):
+        j = 0
+        for wd in WIDTH:
+            leaf = next(it)
+            if leaf.grad is not None:
+                out[t, :, j:j + wd] = leaf.grad.cpu().reshape(B, wd, H * W)
+            j += wd
+    return out
+
+
+def _bits(x):
+    return x.detach().cpu().contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["planes", "packed"])
+@pytest.mark.parametrize("scenario", ["half", "empty_task"])
+@pytest.mark.parametrize("nb", [10, 8])
+def test_rotated_terms_match_float64(hip_lib, nb, scenario, packed):
+    from unidistill_amd.ops import det_loss
+    c = _case(nb, scenario)
+    dev = lambda v: v.cuda()
+    ind, mask, tgt, num_obj = dev(c["ind"]), dev(c["mask"]), dev(c["tgt"]), dev(c["num_obj"])
+    w_box, w_iou, w_aw = (dev(v.float()) for v in c["w"])
+    preds, leaves, slots = _preds(c["planes"], packed)
+    box, il, aw = det_loss.reg_terms(preds, ind, mask, tgt, num_obj, SX, SY, nb, iou_mode="rotated3d")
+    ((box * w_box).sum() + (il * w_iou).sum() + (aw * w_aw).sum()).backward()
+    grads = _plane_grads(leaves, slots, packed)
+    # the box L1 is the reference mode's, bit for bit (NaN of the NaN velocity target included); so is the default call
+    with torch.no_grad():
+        ref = det_loss.reg_terms(preds, ind, mask, tgt, num_obj, SX, SY, nb, iou_mode="reference")
+        dflt = det_loss.reg_terms(preds, ind, mask, tgt, num_obj, SX, SY, nb)
+    assert torch.equal(_bits(box), _bits(ref[0]))
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(ref, dflt))
+    if nb == 10:
+        assert bool(torch.isnan(box[0, 8])) and int(torch.isnan(box).sum()) == 1
+    # losses and gradients against the float64 restatement
+    il64, aw64, g64, margin = c["f64"]
+    il32, aw32, g32, _ = c["f32"]
+    ok = (margin >= R.MARGIN) & c["mask"]
+    tol_l = max(4 * max(float((il32 - il64).abs().max()), float((aw32 - aw64).abs().max())), 1e-6)
+    tol_g = max(4 * float((g32 - g64)[ok].abs().max()), 1e-6)
+    dev_l = max(float((il.detach().cpu().double() - il64).abs().max()), float((aw.detach().cpu().double() - aw64).abs().max()))
+    gk = grads.gather(3, c["ind"][:, :, None, :].expand(T, B, 11, K)).permute(0, 1, 3, 2).double()       # [T,B,K,11]
+    dev_g = float((gk - g64)[ok].abs().max())
+    print(f"nb {nb} {scenario}: losses kernel {dev_l:.3e} allowed {tol_l:.3e} (float32 restatement "
+          f"{max(float((il32 - il64).abs().max()), float((aw32 - aw64).abs().max())):.3e}) | gradients kernel {dev_g:.3e} "
+          f"allowed {tol_g:.3e} (float32 restatement {float((g32 - g64)[ok].abs().max()):.3e}) on {int(ok.sum())} of {int(c['mask'].sum())} positive slots")
+    assert dev_l <= tol_l
+    assert dev_g <= tol_g
+    # the yaw outputs do receive an IoU gradient: in the reference mode the same call leaves them the L1's alone
+    preds_r, leaves_r, slots_r = _preds(c["planes"], packed)
+    box_r, il_r, aw_r = det_loss.reg_terms(preds_r, ind, mask, tgt, num_obj, SX, SY, nb, iou_mode="reference")
+    ((box_r * w_box).sum() + (il_r * w_iou).sum() + (aw_r * w_aw).sum()).backward()
+    assert float((grads - _plane_grads(leaves_r, slots_r, packed))[:, :, 6:8].abs().max()) > 1e-4
+    assert torch.isfinite(grads).all()
+    # nothing outside the positive slots: masked slots and every other pixel stay exactly zero
+    hit = torch.zeros(T, B, 1, H * W, dtype=torch.bool)
+    hit.scatter_(3, c["ind"][:, :, None, :], c["mask"][:, :, None, :])
+    assert float(grads.masked_fill(hit, 0).abs().max()) == 0.0
+    if scenario == "empty_task":
+        assert float(il[1].detach()) == 0.0 and float(aw[1].detach()) == 0.0 and float(grads[1].abs().max()) == 0.0
+    if nb == 8:
+        assert float(grads[:, :, 8:10].abs().max()) == 0.0
+    # reproducible: a second evaluation is bitwise the same
+    preds2, leaves2, slots2 = _preds(c["planes"], packed)
+    box2, il2, aw2 = det_loss.reg_terms(preds2, ind, mask, tgt, num_obj, SX, SY, nb, iou_mode="rotated3d")
+    ((box2 * w_box).sum() + (il2 * w_iou).sum() + (aw2 * w_aw).sum()).backward()
+    assert torch.equal(_bits(il2), _bits(il)) and torch.equal(_bits(aw2), _bits(aw))
+    assert torch.equal(_plane_grads(leaves2, slots2, packed), grads)
+
+
+def test_nan_box_target_propagates_and_gradients_stay_finite(hip_lib):
+    from unidistill_amd.ops import det_loss
+    c = _case(10, "half")
+    tgt = c["tgt"].clone()
+    tgt[0, 0, 0, 0] = float("nan")                       # the x offset of a positive slot of task 0
+    preds, leaves, slots = _preds(c["planes"], False)
+    dev = lambda v: v.cuda()
+    box, il, aw = det_loss.reg_terms(preds, dev(c["ind"]), dev(c["mask"]), dev(tgt), dev(c["num_obj"]), SX, SY, 10,
+                                     iou_mode="rotated3d")
+    (box.nan_to_num().sum() + il.nan_to_num().sum() + aw.nan_to_num().sum()).backward()
+    assert bool(torch.isnan(il[0])) and bool(torch.isnan(aw[0]))                  # like the box terms: a NaN target shows
+    assert bool(torch.isfinite(il[1])) and bool(torch.isfinite(aw[1]))
+    assert torch.isfinite(_plane_grads(leaves, slots, False)).all()
+
+
+def _head(iou_mode=None):
+    from unidistill_amd.layers import center_head as ch
+    tasks = [dict(num_class=1, class_names=["car"]), dict(num_class=2, class_names=["truck", "bus"])]
+    names = [n for t in tasks for n in t["class_names"]]
+    pc_range, voxel = [-32.0, -32.0, -5.0, 32.0, 32.0, 3.0], [0.25, 0.25, 0.2]
+    assigner = ch.FCOSAssigner(out_size_factor=8, tasks=tasks, dense_reg=1, gaussian_overlap=0.1, max_objs=200, min_radius=2,
+                               mapping={n: i + 1 for i, n in enumerate(names)}, grid_size=[256, 256, 40], pc_range=pc_range[:2],
+                               voxel_size=voxel[:2], assign_topk=9, with_velocity=True)
+    kw = {} if iou_mode is None else {"iou_mode": iou_mode}
+    return ch.CenterHeadIouAware(
+        dataset_name="nuscenes", tasks=tasks, target_assigner=assigner, proposal_layer=None, out_size_factor=8, input_channels=24,
+        grid_size=[256, 256, 40], point_cloud_range=pc_range, code_weights=[1.0] * 8 + [0.2, 0.2], loc_weight=0.25, iou_weight=5.0,
+        share_conv_channel=16,
+        common_heads={"iou": [1, 2], "reg": [2, 2], "height": [1, 2], "dim": [3, 2], "rot": [2, 2], "vel": [2, 2]},
+        voxel_size_xy=voxel[:2], **kw)
+
+
+def _head_inputs(seed=0, Bh=2, M=10):
+    g = torch.Generator().manual_seed(seed)
+    gt = torch.zeros(Bh, M, 10)
+    for b, n in enumerate([M - 2, 3][:Bh]):
+        gt[b, :n, 0:2] = (torch.rand(n, 2, generator=g) * 2 - 1) * 29
+        gt[b, :n, 2] = torch.randn(n, generator=g)
+        gt[b, :n, 3:6] = torch.rand(n, 3, generator=g) * 3 + 0.4
+        gt[b, :n, 6] = (torch.rand(n, generator=g) * 2 - 1) * 3.1
+        gt[b, :n, 7:9] = torch.randn(n, 2, generator=g)
+        gt[b, :n, 9] = torch.randint(1, 4, (n,), generator=g).float()
+    return gt.cuda(), torch.randn(Bh, 24, 32, 32, generator=g).cuda()
+
+
+def _head_loss(head, gt, feat):
+    head.train()
+    head.zero_grad()
+    ret = head(feat.clone(), gt.clone())
+    for enc in ret["box_encoding"].values():
+        enc[torch.isinf(enc)] = 0
+    outs = {f"{t}.{k}": v for t, pd in enumerate(ret["multi_head_features"]) for k, v in pd.items()}
+    for v in outs.values():
+        v.retain_grad()
+    loss, tb = head.get_loss(ret)
+    loss.backward()
+    # gradients by the head outputs come straight from the loss kernels (reproducible); the parameters' pass library convolutions
+    return (loss.detach(), {n: p.grad.clone() for n, p in head.named_parameters() if p.grad is not None},
+            {k: v.grad.clone() for k, v in outs.items()})
+
+
+def test_head_in_rotated_mode(hip_lib, lenient):
+    gt, feat = _head_inputs()
+    torch.manual_seed(0)
+    head = _head("rotated3d").cuda()
+    assert head.iou_mode == "rotated3d"
+    loss, grads, douts = _head_loss(head, gt, feat)
+    assert bool(torch.isfinite(loss))
+    for n, p in head.named_parameters():
+        assert n in grads and bool(torch.isfinite(grads[n]).all()), n          # every parameter is reached, the rot head's too
+    # "reference" is the constructor default, bit for bit
+    res = []
+    for kw in (None, "reference"):
+        torch.manual_seed(0)
+        h = _head(kw).cuda()
+        assert h.iou_mode == "reference"
+        res.append(_head_loss(h, gt, feat))
+    assert torch.equal(res[0][0], res[1][0])
+    assert res[0][2].keys() == res[1][2].keys() and all(torch.equal(res[0][2][k], res[1][2][k]) for k in res[0][2])
+    # the two modes do differ: same weights, other IoU terms
+    head.set_iou_mode("reference")
+    loss_ref, _, douts_ref = _head_loss(head, gt, feat)
+    assert not torch.equal(loss_ref, loss)
+    assert all(torch.equal(douts_ref[k], res[0][2][k]) for k in douts_ref)            # switching back restores the default exactly
+
+
+def test_mode_errors_and_plumbing(hip_lib, lenient):
+    from unidistill_amd import config, train
+    from unidistill_amd.ops import det_loss
+    with pytest.raises(ValueError, match="iou_mode"):
+        _head("rotated")
+    with pytest.raises(ValueError, match="iou_mode"):
+        _head().set_iou_mode("3d")
+    c = _case(10, "half")
+    preds, _, _ = _preds(c["planes"], False)
+    dev = lambda v: v.cuda()
+    with pytest.raises(ValueError, match="iou_mode"):
+        det_loss.reg_terms(preds, dev(c["ind"]), dev(c["mask"]), dev(c["tgt"]), dev(c["num_obj"]), SX, SY, 10, iou_mode="bev")
+    # no CPU fallback: the head names device and dtype, the op refuses CPU tensors
+    head = _head("rotated3d").train()
+    gt, feat = _head_inputs()
+    ret = head(feat.cpu(), gt.cpu())
+    for enc in ret["box_encoding"].values():
+        enc[torch.isinf(enc)] = 0
+    with pytest.raises(ValueError, match=r"rotated3d.*cpu.*float32"):
+        head.get_loss(ret)
+    cpu_preds = [{k: v.detach().cpu() for k, v in pd.items()} for pd in preds]
+    with pytest.raises(RuntimeError, match="GPU only"):
+        det_loss.reg_terms(cpu_preds, c["ind"], c["mask"], c["tgt"], c["num_obj"], SX, SY, 10, iou_mode="rotated3d")
+    # plumbing: config -> model -> head, and the training steps set the student's head only
+    assert "iou_mode" not in config.model_cfg()["det_head"]
+    assert config.model_cfg(iou_mode="rotated3d")["det_head"]["iou_mode"] == "rotated3d"
+    step = train.DetectStep("camera", iou_mode="rotated3d")
+    assert step.model.det_head.dense_head.iou_mode == "rotated3d"
+    assert train.DetectStep(model=step.model).model.det_head.dense_head.iou_mode == "rotated3d"       # None: no change
+    teacher = torch.nn.Module()                          # stands in for a teacher: a head and nothing else
+    teacher.det_head = torch.nn.Module()
+    teacher.det_head.dense_head = _head()
+    dstep = train.DistillStep("camera_exp_distill_lidar", student=step.model, teacher=teacher, iou_mode="reference")
+    assert dstep.model.det_head.dense_head.iou_mode == "reference"
+    dstep = train.DistillStep("camera_exp_distill_lidar", student=step.model, teacher=teacher, iou_mode="rotated3d")
+    assert dstep.model.det_head.dense_head.iou_mode == "rotated3d"
+    assert dstep.teacher_model.det_head.dense_head.iou_mode == "reference"
