@@ -2,9 +2,14 @@
 
 The library is a plain C ABI (no torch types).  torch is imported first so that the HIP runtime
 (libamdhip64.so.7) already mapped by torch is the one our library binds to.
+
+The signatures are not written down here: they are parsed from the prototypes of include/unidistill_hip.h at import.
+`load()` is the raw CDLL with those argtypes (a call returns its status); `ud` holds the same functions for the product
+path: a tensor is accepted wherever the header has a pointer, and a non-zero status raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -12,228 +17,91 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libunidistill_hip.so")
 _cdll = None
 
-c_void_p, c_int, c_size_t, c_uint, c_i64, c_float = (
-    ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint, ctypes.c_int64, ctypes.c_float)
+c_void_p, c_int = ctypes.c_void_p, ctypes.c_int
 
-# name -> (restype, argtypes); mirrors include/unidistill_hip.h one to one.
-_SIGS = {
-    "ud_version": (ctypes.c_char_p, []),
-    "ud_abi_version": (c_int, []),
-    "ud_error_string": (ctypes.c_char_p, [c_int]),
-    "ud_prof_enable": (None, [c_int]),
-    "ud_prof_read": (c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), c_int]),
-    "ud_bench_stream": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "ud_bev_pool_workspace_bytes": (c_size_t, [c_int] * 6),
-    "ud_bev_pool_fwd": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_uint, c_void_p, c_size_t, c_void_p]),
-    "ud_bev_pool_bwd_workspace_bytes": (c_size_t, [c_int] * 4 + [c_i64]),
-    "ud_bev_pool_bwd": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p, c_void_p] + [c_int] * 5
-                        + [c_void_p, c_size_t, c_void_p]),
-    "ud_lss_prepare_mats": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p]),
-    "ud_lss_geometry": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p,
-                                                              c_void_p, c_void_p]),
-    "ud_lss_depth_ctx": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 5 + [c_void_p] * 3),
-    "ud_lss_lift_fwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
-    "ud_lss_splat_fwd": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
-    "ud_lss_splat_geom_fwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
-    "ud_lss_lift_bwd_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_lss_lift_bwd": (c_int, [c_void_p] * 5 + [c_i64] * 4 + [c_int] * 8
-                        + [c_void_p, c_size_t, c_void_p]),
-    "ud_spconv_index_bytes": (c_size_t, [c_int] * 5),
-    "ud_spconv_build_index": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
-    "ud_spconv_build_index_dev": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
-    "ud_spconv_down_outputs_dev": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3
-                                   + [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
-    "ud_spconv_subm_rulebook": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
-    "ud_spconv_down_outputs": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 3
-                               + [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
-    "ud_spconv_down_rulebook": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3
-                                + [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "ud_spconv_conv": (c_int, [c_void_p] * 3 + [c_i64] * 3 + [c_int, c_void_p, c_void_p]
-                       + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "ud_spconv_conv_bf16io": (c_int, [c_void_p] * 3 + [c_i64] * 3 + [c_int, c_void_p, c_void_p]
-                              + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "ud_spconv_wgrad_workspace_bytes": (c_size_t, [c_int] * 4),
-    "ud_spconv_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_spconv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int] * 4),
-    "ud_spconv_wgrad_bf16": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_size_t,
-                                                                   c_void_p]),
-    "ud_spconv_mask_order_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "ud_spconv_mask_order": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_spconv_tile_masks": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ud_sparse_bev_workspace_bytes": (c_size_t, [c_int] * 4),
-    "ud_sparse_to_bev_bf16": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_sparse_to_bev_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_bev_to_sparse_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_bev_to_sparse_bf16": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_sparse_to_dense": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_dense_to_sparse": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_distill_box_corners": (c_int, [c_void_p, c_int, c_int, c_int] + [ctypes.c_double] * 4
-                               + [c_void_p, c_void_p, c_void_p]),
-    "ud_distill_box_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-                           + [c_int] * 5 + [c_void_p, c_void_p]),
-    "ud_distill_box_bwd_workspace_bytes": (c_size_t, [c_int] * 3),
-    "ud_distill_box_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-                           + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_distill_box_bwd_acc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-                               + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_distill_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "ud_distill_gaussian_mask": (c_int, [c_void_p, c_int, c_int, c_int] + [ctypes.c_double] * 4
-                                 + [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_distill_resp_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_int, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                                    c_void_p, c_void_p]),
-    "ud_distill_resp_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float,
-                                    c_float, c_void_p, c_void_p, c_void_p]),
-    "ud_distill_resp_fwd_strided": (c_int, [c_void_p] * 4 + [c_void_p, c_int] + [c_void_p] * 4 + [c_void_p, c_int, c_void_p,
-                                            c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
-    "ud_distill_resp_bwd_strided": (c_int, [c_void_p] * 6 + [c_void_p, c_int] + [c_void_p] * 6 + [c_void_p, c_int, c_void_p,
-                                            c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
-    "ud_voxelize_workspace_bytes": (c_size_t, [c_int] * 4),
-    "ud_voxelize_capacity": (c_int, [c_int] * 3),
-    "ud_voxelize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int]
-                    + [c_void_p] * 5 + [c_void_p, c_size_t, c_int, c_void_p]),
-    "ud_conv3x3_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p]),
-    "ud_conv1x1_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
-    "ud_conv3x3_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p]),
-    "ud_conv1x1_nhwc_f32": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
-    "ud_conv3x3_bnstats_bytes": (c_size_t, [c_int] * 4),
-    "ud_conv1x1_bnstats_bytes": (c_size_t, [c_i64, c_int]),
-    "ud_conv3x3_bnstats_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2 + [c_size_t, c_void_p, c_void_p]),
-    "ud_conv1x1_bnstats_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 2 + [c_size_t, c_void_p, c_void_p]),
-    "ud_conv3x3_bnstats_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2 + [c_size_t, c_void_p, c_void_p]),
-    "ud_conv1x1_bnstats_nhwc_f32": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 2 + [c_size_t, c_void_p, c_void_p]),
-    "ud_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_conv3x3_wgrad_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_points_transform": (c_int, [c_void_p] * 5 + [c_int, c_int, c_i64, c_void_p]),
-    "ud_conv1x1_mapped_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 3),
-    "ud_conv1x1_mapped_nhwc_f32": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 3),
-    "ud_conv1x1p_f32_workspace_bytes": (c_size_t, []),
-    "ud_conv1x1_f32_persistent": (None, [c_int]),
-    "ud_conv1x1p_stream_k": (None, [c_int]),
-    "ud_conv1x1_f32_persistent_enabled": (c_int, []),
-    "ud_conv1x1p_nhwc_f32": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_size_t, c_void_p]
-                             + [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "ud_conv1x1_wgrad_mapped_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 2
-                                          + [c_void_p, c_size_t, c_void_p]),
-    "ud_image_normalize": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "ud_collate_pad": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p]),
-    "ud_image_affine_workspace_bytes": (c_size_t, [c_void_p, c_int]),
-    "ud_image_affine_check": (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_i64, c_int, c_int, c_size_t]),
-    "ud_image_affine": (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, c_void_p, c_void_p] + [c_int] * 4
-                        + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
-    "ud_lidar_prep_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
-    "ud_lidar_prep_count": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
-                            + [c_size_t, c_void_p]),
-    "ud_lidar_prep_compact": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6
-                              + [c_i64, c_int, c_void_p, c_i64, c_void_p, c_size_t, c_void_p]),
-    "ud_jpeg_parse": (c_int, [c_void_p, c_i64, c_void_p]),
-    "ud_jpeg_plan": (c_size_t, [c_void_p, c_int]),
-    "ud_jpeg_decode": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p,
-                               c_void_p, c_size_t, c_void_p]),
-    "ud_nus_pred_to_global": (c_int, [c_void_p, c_i64, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_int]
-                              + [c_void_p] * 7),
-    "ud_nus_eval_workspace_bytes": (c_size_t, [c_i64, c_int]),
-    "ud_nus_eval": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_size_t, c_void_p]),
-    "ud_stem_pack_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p]),
-    "ud_stem_conv7x7_bn_relu": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_void_p]),
-    "ud_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
-    "ud_conv1x1_wgrad_workspace_bytes": (c_size_t, [c_i64, c_int, c_int]),
-    "ud_conv3x3_wgrad_f32_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_conv3x3_wgrad_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_conv1x1_wgrad_f32_workspace_bytes": (c_size_t, [c_i64, c_int, c_int]),
-    "ud_conv1x1_wgrad_mapped_nhwc_f32": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p] * 2
-                                         + [c_void_p, c_size_t, c_void_p]),
-    "ud_conv3x3_wino4_f32_weight_bytes": (c_size_t, [c_int, c_int]),
-    "ud_conv3x3_wino4_bnstats_bytes": (c_size_t, [c_int] * 4),
-    "ud_conv3x3_wino4_f32_blocks": (c_int, [c_int, c_int]),
-    "ud_conv3x3_wino4_f32_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "ud_conv3x3_wino4_f32_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_conv3x3_wino4_stream_k": (None, [c_int]),
-    "ud_conv3x3_wino4_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p, c_size_t,
-                                                                                              c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_conv3x3_wino_f32_weight_bytes": (c_size_t, [c_int, c_int]),
-    "ud_conv3x3_wino_bnstats_bytes": (c_size_t, [c_int] * 4),
-    "ud_conv3x3_wino4_wgrad_f32_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_conv3x3_wino4_wgrad_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_conv3x3_wino_wgrad_f32_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_conv3x3_wino_wgrad_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_conv3x3_wino_f32_blocks": (c_int, [c_int, c_int]),
-    "ud_conv3x3_wino_f32_weights": (c_int, [c_void_p] + [c_i64] * 4 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "ud_conv3x3_wino_nhwc_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p, c_size_t,
-                                                                                        c_void_p, c_void_p]),
-    "ud_conv1x1_wgrad_nhwc_bf16": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int] + [c_void_p, c_size_t, c_void_p]),
-    "ud_assign_targets": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p] + [c_int] * 8 + [c_float] * 5
-                          + [c_void_p] * 6),
-    "ud_det_loss_workspace_bytes": (c_size_t, [c_int]),
-    "ud_det_focal_fwd": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_float, c_float, c_void_p, c_void_p,
-                                                                c_void_p, c_size_t, c_void_p]),
-    "ud_det_focal_bwd": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 5 + [c_float, c_float, c_void_p,
-                                                                              c_void_p]),
-    "ud_det_reg_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int,
-                                                                     c_void_p, c_float, c_float, c_void_p,
-                                                                     c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_det_reg_bwd": (c_int, [c_int] * 5 + [c_void_p] * 8),
-    "ud_det_reg_fwd_rot": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int,
-                                                                         c_void_p, c_float, c_float, c_void_p,
-                                                                         c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_det_reg_bwd_rot": (c_int, [c_int] * 5 + [c_void_p] * 8),
-    "ud_rot_iou3d_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "ud_nms_bev_workspace_bytes": (c_size_t, [c_int]),
-    "ud_nms_rotated_bev": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_boxes_iou_bev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "ud_proposal_workspace_bytes": (c_size_t, [c_int] * 3),
-    "ud_proposal_layer": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_float] * 5 + [c_void_p, c_float, c_float]
-                          + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]),
-    "ud_bn_act_workspace_bytes": (c_size_t, [c_int]),
-    "ud_bn_stats": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 7
-                    + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_bn_stats_from_partials": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 7
-                                  + [c_float, c_void_p, c_void_p]),
-    "ud_bn_act_fwd": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_void_p]),
-    "ud_bn_act_bwd": (c_int, [c_void_p] * 11 + [c_i64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "ud_head_tail_f32_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "ud_head_tail_f32_bn_fwd": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "ud_head_tail_f32_bn_wgrad": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_head_tail_f32_dgrad": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
-    "ud_head_tail_f32_bn_bwd_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_head_tail_f32_bn_bwd": (c_int, [c_void_p] * 11 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_colsum_workspace_bytes": (c_size_t, [c_int]),
-    "ud_colsum_f32": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_colsum_bf16": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_head_tail_f32_wgrad_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ud_head_tail_f32_wgrad": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_bn_stats_f32": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 7
-                        + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_bn_act_fwd_f32": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_void_p]),
-    "ud_bn_act_bwd_f32": (c_int, [c_void_p] * 11 + [c_i64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "ud_bn_act_fwd_ld": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_i64, c_int, c_void_p]),
-    "ud_bn_act_fwd_ld_f32": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_i64, c_int, c_void_p]),
-    "ud_bn_act_bwd_ld": (c_int, [c_void_p] * 3 + [c_i64] + [c_void_p] * 8 + [c_i64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "ud_bn_act_bwd_ld_f32": (c_int, [c_void_p] * 3 + [c_i64] + [c_void_p] * 8 + [c_i64, c_int, c_int, c_void_p, c_size_t,
-                                                                                 c_void_p]),
-    "ud_head_tail_workspace_bytes": (c_size_t, [c_int]),
-    "ud_head_tail_stats": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_float]
-                           + [c_void_p] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_head_tail_fwd": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "ud_head_tail_bwd": (c_int, [c_void_p] * 11 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "ud_optim_chunk_elems": (c_int, []),
-    "ud_optim_sqnorm": (c_int, [c_void_p, c_int] + [c_void_p] * 4),
-    "ud_optim_clip_adamw": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [ctypes.c_double] * 5 + [c_int, c_void_p]),
-    "ud_optim_clip_adamw_ema": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [ctypes.c_double] * 5 + [c_int]
-                                + [ctypes.c_double] * 2 + [c_void_p]),
-    "ud_optim_swap": (c_int, [c_void_p, c_int] + [c_void_p] * 3),
-    "ud_depth_labels_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "ud_depth_labels": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int] + [c_void_p] * 4 + [c_int] * 4
-                        + [ctypes.c_double] * 3 + [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_depth_loss_workspace_bytes": (c_size_t, [c_int] * 3),
-    "ud_depth_loss_fwd": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ud_depth_loss_bwd": (c_int, [c_void_p] + [c_i64] * 4 + [c_void_p] * 4 + [c_i64] * 4 + [c_int] * 4 + [c_void_p]),
+HEADER_PATH = os.path.join(_HERE, "..", "..", "include", "unidistill_hip.h")
+
+_SCALARS = {
+    "void": None, "int": c_int, "int32_t": c_int, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint,
+    "int64_t": ctypes.c_int64, "long long": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+    "double": ctypes.c_double, "ud_stream_t": c_void_p,
 }
+# Out-parameters that Python passes with byref() of a typed scalar; every other pointer is an address (c_void_p).
+_TYPED_POINTERS = {"ud_prof_read": {"double *": ctypes.POINTER(ctypes.c_double), "int *": ctypes.POINTER(c_int)}}
+# Entry points whose int result is a value (a count, a flag, ud_jpeg_parse's positive codes), not a UD_ERR_* status.
+VALUE_RETURNS = ("ud_abi_version", "ud_voxelize_capacity", "ud_optim_chunk_elems", "ud_conv1x1_f32_persistent_enabled",
+                 "ud_conv3x3_wino4_f32_blocks", "ud_conv3x3_wino_f32_blocks", "ud_jpeg_parse")
+
+_PROTO = re.compile(r"([^;{}()]*?)\b(ud_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl, proto, named):
+    """ctypes type of one C declarator (`const float* x`, `long long P`, a bare return type); raises on an unknown spelling."""
+    toks = [t for t in re.findall(r"\w+|\*|\S", decl) if t != "const"]
+    if "*" in toks:
+        spelled = " ".join(toks[:len(toks) - toks[::-1].index("*")])
+        typed = _TYPED_POINTERS.get(proto, {}).get(spelled)
+        return typed or (ctypes.c_char_p if spelled == "char *" else c_void_p)
+    if named and len(toks) > 1 and " ".join(toks) not in _SCALARS:
+        toks = toks[:-1]  # the parameter's name
+    if " ".join(toks) not in _SCALARS:
+        raise ValueError(f"unidistill_hip.h: unknown type {decl.strip()!r} in the prototype of {proto}")
+    return _SCALARS[" ".join(toks)]
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every ud_* prototype in the header text."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _PROTO.findall(text):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_ctype(ret, name, False), [_ctype(p, name, True) for p in params])
+    stray = set(re.findall(r"\b(ud_[a-z0-9_]+)\s*\(", text)) - set(sigs)
+    if stray:
+        raise ValueError(f"unidistill_hip.h: cannot parse the prototype of {sorted(stray)[0]}")
+    return sigs
+
+
+with open(HEADER_PATH) as _f:
+    _PROTOTYPES = parse_header(_f.read())
+assert set(VALUE_RETURNS) <= set(_PROTOTYPES), sorted(set(VALUE_RETURNS) - set(_PROTOTYPES))
 
 
 class HipLibraryMissing(RuntimeError):
     pass
+
+
+class _TensorPointer:
+    """c_void_p argtype of the checked functions: a tensor goes in as its address (the call's argument tuple keeps it alive
+    until the C function returns); None, ints, ctypes arrays and byref() convert as for c_void_p.  The device is not looked
+    at (some entry points take host buffers; require_gpu is the callers' check)."""
+
+    @staticmethod
+    def from_param(v, _tensor=torch.Tensor, _pointer=c_void_p.from_param):
+        # c_void_p.from_param makes a pointer-sized parameter of the address without building a Python-level c_void_p
+        # (host cost per argument: the wrappers are launch-bound); a bare int returned from here would go in as a 32-bit C int
+        return _pointer(v.data_ptr() if isinstance(v, _tensor) else v)
+
+
+def _raise_on_error(code, fn, args):
+    if code:
+        check(code, fn.__name__)
+    return code
+
+
+class _CheckedLibrary:
+    """`_lib.ud`: every entry point once more, taking tensors for pointers and raising on a non-zero status."""
+
+    def __getattr__(self, name):  # only reached while load() has not filled the instance yet
+        if _cdll is None:
+            load()
+            return getattr(self, name)
+        raise AttributeError(name)
+
+
+ud = _CheckedLibrary()
 
 
 def load():
@@ -245,16 +113,21 @@ def load():
                 f"{LIB_PATH} not found: build it with `make -C cvpr2023-unidistill_amd` "
                 "(or __graft_entry__.build()). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in _PROTOTYPES.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype, fn.argtypes = res, args
+            checked = lib[name]  # a second function object: the raw one keeps returning its status
+            checked.restype = res
+            checked.argtypes = [_TensorPointer if a is c_void_p else a for a in args]
+            if res is c_int and name not in VALUE_RETURNS:
+                checked.errcheck = _raise_on_error
+            setattr(ud, name, checked)
         _cdll = lib
     return _cdll
 
 
 def exported_symbols():
-    return sorted(_SIGS)
+    return sorted(_PROTOTYPES)
 
 
 def check(code, what):

@@ -191,12 +191,10 @@ class FCOSAssigner:
         mask = torch.empty((T, B, K), dtype=torch.bool, device=dev)
         cat = torch.empty((T, B, K), dtype=torch.long, device=dev)
         enc = torch.empty((T, B, K, enc_dim), dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        _lib.check(lib.ud_assign_targets(_lib.ptr(gt), B, M, cols, tabs[0], tabs[1], ncls, T, ncmax, w, h, K, topk,
-                                         enc_dim, float(self.out_size_factor), float(self.pc_range[0]),
-                                         float(self.pc_range[1]), float(self.voxel_size[0]),
-                                         float(self.voxel_size[1]), _lib.ptr(hm), _lib.ptr(ind), _lib.ptr(mask),
-                                         _lib.ptr(cat), _lib.ptr(enc), _lib.stream_of(gt)), "ud_assign_targets")
+        _lib.ud.ud_assign_targets(gt, B, M, cols, tabs[0], tabs[1], ncls, T, ncmax, w, h, K, topk, enc_dim,
+                                  float(self.out_size_factor), float(self.pc_range[0]), float(self.pc_range[1]),
+                                  float(self.voxel_size[0]), float(self.voxel_size[1]), hm, ind, mask, cat, enc,
+                                  _lib.stream_of(gt))
         out = {k: {} for k in ("heatmap", "ind", "mask", "cat", "box_encoding")}
         for t, names in enumerate(self.task_classes):
             out["heatmap"][t] = hm[t, :, :len(names)].contiguous() if len(names) != ncmax else hm[t]

@@ -93,12 +93,11 @@ class CenterPointGenProposals(nn.Module):
         c_off = (ctypes.c_int * T)(*class_offsets)
         c_alpha = (ctypes.c_float * T)(*alphas) if alphas is not None else None
         c_rng = (ctypes.c_float * 6)(*[float(v) for v in self.post_center_limit_range])
-        _lib.check(lib.ud_proposal_layer(
-            c_ptrs, c_str, c_nc, c_off, c_alpha, B, T, H, W, K, post, nbox, 1 if self.no_log else 0,
-            float(self.out_size_factor), float(self.voxel_size[0]), float(self.voxel_size[1]),
-            float(self.pc_range[0]), float(self.pc_range[1]), c_rng, float(self.score_threshold),
-            float(self.nms_iou_threshold_use), _lib.ptr(rois), _lib.ptr(scores), _lib.ptr(labels),
-            _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_of(hm0)), "ud_proposal_layer")
+        _lib.ud.ud_proposal_layer(c_ptrs, c_str, c_nc, c_off, c_alpha, B, T, H, W, K, post, nbox, 1 if self.no_log else 0,
+                                  float(self.out_size_factor), float(self.voxel_size[0]), float(self.voxel_size[1]),
+                                  float(self.pc_range[0]), float(self.pc_range[1]), c_rng, float(self.score_threshold),
+                                  float(self.nms_iou_threshold_use), rois, scores, labels, counts, ws, ws.numel(),
+                                  _lib.stream_of(hm0))
         return rois, scores, labels, counts
 
     def _phase(self):

@@ -36,9 +36,7 @@ def _pool_fwd(geom, feat, out, pos, B, N, C, nx, ny, nz, flags):
     if need == 0:
         raise ValueError("invalid voxel pooling sizes")
     ws = _lib.workspace(feat.device, need, "bev_pool")
-    _lib.check(lib.ud_bev_pool_fwd(_lib.ptr(geom), _lib.ptr(feat), _lib.ptr(out), _lib.ptr(pos),
-                                   B, N, C, nx, ny, nz, flags, _lib.ptr(ws), ws.numel(),
-                                   _lib.stream_of(feat)), "ud_bev_pool_fwd")
+    _lib.ud.ud_bev_pool_fwd(geom, feat, out, pos, B, N, C, nx, ny, nz, flags, ws, ws.numel(), _lib.stream_of(feat))
 
 
 def _pool_bwd(gout, pos, B, N, C, nx, ny):
@@ -51,9 +49,7 @@ def _pool_bwd(gout, pos, B, N, C, nx, ny):
     sb, sc, sy, sx = gout.stride()
     need = lib.ud_bev_pool_bwd_workspace_bytes(B, C, nx, ny, sc)
     ws = _lib.workspace(gout.device, need, "bev_pool_bwd")
-    _lib.check(lib.ud_bev_pool_bwd(_lib.ptr(gout), sb, sc, sy, sx, _lib.ptr(pos), _lib.ptr(gfeat),
-                                   B, N, C, nx, ny, _lib.ptr(ws), ws.numel(),
-                                   _lib.stream_of(gout)), "ud_bev_pool_bwd")
+    _lib.ud.ud_bev_pool_bwd(gout, sb, sc, sy, sx, pos, gfeat, B, N, C, nx, ny, ws, ws.numel(), _lib.stream_of(gout))
     return gfeat
 
 

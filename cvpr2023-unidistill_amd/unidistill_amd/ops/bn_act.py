@@ -51,10 +51,9 @@ def _workspace(dev, C):
 def batch_stats(x, gamma, beta, running_mean, running_var, training, momentum, eps, tracked=None, partial=None):
     """-> f32 [5, C]: mean, var, invstd, scale, shift of BatchNorm over x ([B, C, H, W] channels-last or [M, C]); training: batch
     statistics (from the producing convolution's per-tile partials when given) and the running buffers updated; eval: running."""
-    lib = _lib.load()
     _lib.require_gpu(x, gamma, beta)
     f32 = x.dtype == torch.float32
-    k_stats = lib.ud_bn_stats_f32 if f32 else lib.ud_bn_stats
+    k_stats = _lib.ud.ud_bn_stats_f32 if f32 else _lib.ud.ud_bn_stats
     C = x.shape[1]
     P = x.numel() // C
     dev = x.device
@@ -70,16 +69,12 @@ def batch_stats(x, gamma, beta, running_mean, running_var, training, momentum, e
         rm, rv = (running_mean, running_var) if fp32_buffers else (None, None)   # updated in-kernel
         if partial is not None and partial[2] == P:
             # the producing convolution already reduced every tile (ud_conv*_bnstats_nhwc_*): second pass only
-            _lib.check(lib.ud_bn_stats_from_partials(partial[0].data_ptr(), int(partial[1]), P, C, g32.data_ptr(),
-                                                     b32.data_ptr(), float(eps), v0, v0 + row, v0 + 2 * row,
-                                                     v0 + 3 * row, v0 + 4 * row, _lib.ptr(rm), _lib.ptr(rv),
-                                                     float(momentum or 0.0), _lib.ptr(tracked), stream),
-                       "ud_bn_stats_from_partials")
+            _lib.ud.ud_bn_stats_from_partials(partial[0].data_ptr(), int(partial[1]), P, C, g32.data_ptr(), b32.data_ptr(),
+                                              float(eps), v0, v0 + row, v0 + 2 * row, v0 + 3 * row, v0 + 4 * row, rm, rv,
+                                              float(momentum or 0.0), tracked, stream)
         else:
-            _lib.check(k_stats(x.data_ptr(), P, C, g32.data_ptr(), b32.data_ptr(), float(eps),
-                               v0, v0 + row, v0 + 2 * row, v0 + 3 * row, v0 + 4 * row,
-                               _lib.ptr(rm), _lib.ptr(rv), float(momentum or 0.0),
-                               _lib.ptr(tracked), ws.data_ptr(), ws.numel(), stream), "ud_bn_stats")
+            k_stats(x.data_ptr(), P, C, g32.data_ptr(), b32.data_ptr(), float(eps), v0, v0 + row, v0 + 2 * row, v0 + 3 * row,
+                    v0 + 4 * row, rm, rv, float(momentum or 0.0), tracked, ws.data_ptr(), ws.numel(), stream)
         if rm is not None:       # written through raw pointers by the statistics kernel: tell autograd's version counters
             torch.autograd.graph.increment_version(rm)
             torch.autograd.graph.increment_version(rv)
@@ -147,9 +142,8 @@ def bias_grad(gy):
     lib = _lib.load()
     out = torch.empty(C, dtype=torch.float32, device=gy.device)
     ws = _lib.workspace(gy.device, lib.ud_colsum_workspace_bytes(C), "colsum")
-    fn = lib.ud_colsum_f32 if gy.dtype == torch.float32 else lib.ud_colsum_bf16
-    _lib.check(fn(gy.data_ptr(), gy.numel() // C, C, C, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_of(gy)),
-               "ud_colsum")
+    fn = _lib.ud.ud_colsum_f32 if gy.dtype == torch.float32 else _lib.ud.ud_colsum_bf16
+    fn(gy.data_ptr(), gy.numel() // C, C, C, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_of(gy))
     return out
 
 
@@ -157,8 +151,7 @@ class _BnActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, training, momentum, eps, relu,
                 tracked=None, partial=None, out=None):
-        lib = _lib.load()
-        k_fwd = lib.ud_bn_act_fwd_ld_f32 if x.dtype == torch.float32 else lib.ud_bn_act_fwd_ld
+        k_fwd = _lib.ud.ud_bn_act_fwd_ld_f32 if x.dtype == torch.float32 else _lib.ud.ud_bn_act_fwd_ld
         C = x.shape[1]
         P = x.numel() // C
         stream = _lib.stream_of(x)
@@ -171,8 +164,7 @@ class _BnActFn(torch.autograd.Function):
         ld = C if out is None else _row_stride(y, x)
         if ld is None:
             raise ValueError(f"bn_act: out {tuple(y.shape)} strides {tuple(y.stride())} is not a channel slice of a channels-last map")
-        _lib.check(k_fwd(x.data_ptr(), _lib.ptr(residual), v0 + 3 * row, v0 + 4 * row,
-                                     y.data_ptr(), P, C, ld, 1 if relu else 0, stream), "ud_bn_act_fwd_ld")
+        k_fwd(x.data_ptr(), residual, v0 + 3 * row, v0 + 4 * row, y.data_ptr(), P, C, ld, 1 if relu else 0, stream)
         ctx.cfg = (bool(training), bool(relu), residual is not None)
         ctx.save_for_backward(x, y if (residual is not None and relu) else None, vec)
         return y
@@ -185,7 +177,6 @@ class _BnActFn(torch.autograd.Function):
             raise NotImplementedError("fused BatchNorm backward covers training-mode statistics only")
         if y is not None and y.stride() != x.stride():
             y = _like(y, x)               # written into a channel slice (out=): the backward kernels read the mask source at p * C + c
-        lib = _lib.load()
         C = x.shape[1]
         P = x.numel() // C
         ld = _row_stride(dy, x)           # a slice of a concatenation's gradient is read in place
@@ -198,11 +189,9 @@ class _BnActFn(torch.autograd.Function):
         dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
         ws = _workspace(x.device, C)
         v0, row, g0 = vec.data_ptr(), 4 * C, dgb.data_ptr()
-        k_bwd = lib.ud_bn_act_bwd_ld_f32 if x.dtype == torch.float32 else lib.ud_bn_act_bwd_ld
-        _lib.check(k_bwd(x.data_ptr(), _lib.ptr(y), dy.data_ptr(), ld, v0 + 3 * row, v0 + 4 * row,
-                                     v0, v0 + 2 * row, dx.data_ptr(), _lib.ptr(dres),
-                                     g0, g0 + row, P, C, 1 if relu else 0,
-                                     ws.data_ptr(), ws.numel(), _lib.stream_of(x)), "ud_bn_act_bwd_ld")
+        k_bwd = _lib.ud.ud_bn_act_bwd_ld_f32 if x.dtype == torch.float32 else _lib.ud.ud_bn_act_bwd_ld
+        k_bwd(x.data_ptr(), y, dy.data_ptr(), ld, v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row, dx.data_ptr(), dres, g0, g0 + row,
+              P, C, 1 if relu else 0, ws.data_ptr(), ws.numel(), _lib.stream_of(x))
         if has_res and ctx.needs_input_grad[3] and dres is None:
             dres = dy
         return dx, dgb[0], dgb[1], dres, None, None, None, None, None, None, None, None, None

@@ -52,15 +52,11 @@ def _launch(x, w_tap, cout, bias=None, scale=None, shift=None, residual=None, re
     if bn_stats:
         lib = _lib.load()
         part, ns = _bn_partial(lib.ud_conv3x3_bnstats_bytes(B, H, W, cout), x.device)
-        _lib.check(lib.ud_conv3x3_bnstats_nhwc_bf16(_lib.ptr(x), _lib.ptr(w_tap), _lib.ptr(y), B, H, W, cin, cout,
-                                                    _lib.ptr(bias), _lib.ptr(part), part.numel() * 4,
-                                                    ctypes.addressof(ns), _lib.stream_of(x)),
-                   "ud_conv3x3_bnstats_nhwc_bf16")
+        _lib.ud.ud_conv3x3_bnstats_nhwc_bf16(x, w_tap, y, B, H, W, cin, cout, bias, part, part.numel() * 4,
+                                             ctypes.addressof(ns), _lib.stream_of(x))
         return y, (part, ns.value, B * H * W)
-    _lib.check(_lib.load().ud_conv3x3_nhwc_bf16(_lib.ptr(x), _lib.ptr(w_tap), _lib.ptr(y), B, H, W, cin,
-                                                cout, _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift),
-                                                _lib.ptr(residual), (1 if relu else 0) | (2 if reverse_taps else 0),
-                                                _lib.stream_of(x)), "ud_conv3x3_nhwc_bf16")
+    _lib.ud.ud_conv3x3_nhwc_bf16(x, w_tap, y, B, H, W, cin, cout, bias, scale, shift, residual,
+                                 (1 if relu else 0) | (2 if reverse_taps else 0), _lib.stream_of(x))
     return y
 
 
@@ -121,9 +117,7 @@ def weight_grad(x, gy, weight):
         need = lib.ud_conv3x3_wgrad_workspace_bytes(B, H, W, cin, cout)
         ws = _lib.workspace(x.device, need, "conv_wgrad")
         dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device)
-        _lib.check(lib.ud_conv3x3_wgrad_nhwc_bf16(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), B, H, W, cin, cout,
-                                                  _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
-                   "ud_conv3x3_wgrad_nhwc_bf16")
+        _lib.ud.ud_conv3x3_wgrad_nhwc_bf16(x, gy, dw, B, H, W, cin, cout, ws, ws.numel(), _lib.stream_of(x))
         return dw.permute(0, 3, 1, 2).to(weight.dtype)
     if USE_HIP_WGRAD == "auto":
         _lib.library_fallthrough("ops.conv2d.weight_grad (3x3 bf16)", x, gy, weight)
@@ -203,9 +197,7 @@ def weight_grad_1x1(x, gy, weight):
     need = lib.ud_conv1x1_wgrad_workspace_bytes(P, cin, cout)
     ws = _lib.workspace(x.device, need, "conv_wgrad")
     dw = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=x.device)
-    _lib.check(lib.ud_conv1x1_wgrad_nhwc_bf16(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), P, cin, cout,
-                                              _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
-               "ud_conv1x1_wgrad_nhwc_bf16")
+    _lib.ud.ud_conv1x1_wgrad_nhwc_bf16(x, gy, dw, P, cin, cout, ws, ws.numel(), _lib.stream_of(x))
     return dw.to(weight.dtype)
 
 
@@ -244,15 +236,11 @@ def _launch1x1(x, w2d, cout, bias=None, scale=None, shift=None, residual=None, r
     if bn_stats:
         lib = _lib.load()
         part, ns = _bn_partial(lib.ud_conv1x1_bnstats_bytes(B * H * W, cout), x.device)
-        _lib.check(lib.ud_conv1x1_bnstats_nhwc_bf16(_lib.ptr(x), _lib.ptr(w2d), _lib.ptr(y), B * H * W, cin, cout,
-                                                    _lib.ptr(bias), _lib.ptr(part), part.numel() * 4,
-                                                    ctypes.addressof(ns), _lib.stream_of(x)),
-                   "ud_conv1x1_bnstats_nhwc_bf16")
+        _lib.ud.ud_conv1x1_bnstats_nhwc_bf16(x, w2d, y, B * H * W, cin, cout, bias, part, part.numel() * 4,
+                                             ctypes.addressof(ns), _lib.stream_of(x))
         return y, (part, ns.value, B * H * W)
-    _lib.check(_lib.load().ud_conv1x1_nhwc_bf16(_lib.ptr(x), _lib.ptr(w2d), _lib.ptr(y), B * H * W, cin, cout,
-                                                _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift),
-                                                _lib.ptr(residual), 1 if relu else 0, _lib.stream_of(x)),
-               "ud_conv1x1_nhwc_bf16")
+    _lib.ud.ud_conv1x1_nhwc_bf16(x, w2d, y, B * H * W, cin, cout, bias, scale, shift, residual, 1 if relu else 0,
+                                 _lib.stream_of(x))
     return y
 
 
@@ -368,11 +356,9 @@ def _mapped(x, w2d, y, P, K, N, imap, omap):
         if _c32.persistent_1x1(K, mapped=True, P=P, N=N) and x.numel() < (1 << 30) - (1 << 18) and y.numel() < (1 << 30) - (1 << 18):
             _c32.launch_1x1p(x, w2d, y, P, K, N, imap=imap, omap=omap)
             return
-        _lib.check(_lib.load().ud_conv1x1_mapped_nhwc_f32(_lib.ptr(x), _lib.ptr(w2d), _lib.ptr(y), P, K, N, imap, omap,
-                                                          _lib.stream_of(x)), "ud_conv1x1_mapped_nhwc_f32")
+        _lib.ud.ud_conv1x1_mapped_nhwc_f32(x, w2d, y, P, K, N, imap, omap, _lib.stream_of(x))
         return
-    _lib.check(_lib.load().ud_conv1x1_mapped_nhwc_bf16(_lib.ptr(x), _lib.ptr(w2d), _lib.ptr(y), P, K, N, imap, omap,
-                                                       _lib.stream_of(x)), "ud_conv1x1_mapped_nhwc_bf16")
+    _lib.ud.ud_conv1x1_mapped_nhwc_bf16(x, w2d, y, P, K, N, imap, omap, _lib.stream_of(x))
 
 
 def _cdt(x):
@@ -389,9 +375,7 @@ def _mapped_wgrad(x, gy, P, K, N, xmap, ymap):
     lib = _lib.load()
     ws = _lib.workspace(x.device, lib.ud_conv1x1_wgrad_workspace_bytes(P, K, N), "conv_wgrad")
     dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    _lib.check(lib.ud_conv1x1_wgrad_mapped_nhwc_bf16(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), P, K, N, xmap, ymap,
-                                                     _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
-               "ud_conv1x1_wgrad_mapped_nhwc_bf16")
+    _lib.ud.ud_conv1x1_wgrad_mapped_nhwc_bf16(x, gy, dw, P, K, N, xmap, ymap, ws, ws.numel(), _lib.stream_of(x))
     return dw
 
 

@@ -98,11 +98,10 @@ def _wino_weights(weight, transposed, f4=False):
     def make():
         n, c = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
         sn, sc = (w.stride(1), w.stride(0)) if transposed else (w.stride(0), w.stride(1))
-        nbytes, fn = ((lib.ud_conv3x3_wino4_f32_weight_bytes, lib.ud_conv3x3_wino4_f32_weights) if f4 else
-                      (lib.ud_conv3x3_wino_f32_weight_bytes, lib.ud_conv3x3_wino_f32_weights))
+        nbytes, fn = ((lib.ud_conv3x3_wino4_f32_weight_bytes, _lib.ud.ud_conv3x3_wino4_f32_weights) if f4 else
+                      (lib.ud_conv3x3_wino_f32_weight_bytes, _lib.ud.ud_conv3x3_wino_f32_weights))
         U = torch.empty(nbytes(c, n) // 4, dtype=torch.float32, device=w.device)
-        _lib.check(fn(_lib.ptr(w), sn, sc, w.stride(2), w.stride(3), n, c, 1 if transposed else 0,
-                      _lib.ptr(U), _lib.stream_of(w)), "ud_conv3x3_wino4_f32_weights" if f4 else "ud_conv3x3_wino_f32_weights")
+        fn(w, sn, sc, w.stride(2), w.stride(3), n, c, 1 if transposed else 0, U, _lib.stream_of(w))
         return U
 
     if weight.requires_grad or torch.cuda.is_current_stream_capturing():
@@ -138,34 +137,27 @@ def _launch3(x, weight, bias=None, relu=False, transposed=False, bn_stats=False,
         if bn_stats:
             part, ns = _bn_partial(lib.ud_conv3x3_wino4_bnstats_bytes(B, H, W, cout), x.device)
         ws = _lib.workspace(x.device, lib.ud_conv3x3_wino4_f32_workspace_bytes(B, H, W, cin, cout), "conv_w4")
-        _lib.check(lib.ud_conv3x3_wino4_nhwc_f32(_lib.ptr(x), _lib.ptr(U), _lib.ptr(y), B, H, W, cin, cout, _lib.ptr(bias),
-                                                 _lib.ptr(scale), _lib.ptr(shift), None, 1 if relu else 0, _lib.ptr(part),
-                                                 part.numel() * 4 if bn_stats else 0, ctypes.addressof(ns), _lib.ptr(ws),
-                                                 ws.numel(), _lib.stream_of(x)),
-                   "ud_conv3x3_wino4_nhwc_f32")
+        _lib.ud.ud_conv3x3_wino4_nhwc_f32(x, U, y, B, H, W, cin, cout, bias, scale, shift, None, 1 if relu else 0, part,
+                                          part.numel() * 4 if bn_stats else 0, ctypes.addressof(ns), ws, ws.numel(),
+                                          _lib.stream_of(x))
         return (y, (part, ns.value, B * H * W)) if bn_stats else y
     if wino_pays(H, W, cin, cout):
         U = _wino_weights(weight, transposed)
         part, ns = (None, ctypes.c_int(0))
         if bn_stats:
             part, ns = _bn_partial(lib.ud_conv3x3_wino_bnstats_bytes(B, H, W, cout), x.device)
-        _lib.check(lib.ud_conv3x3_wino_nhwc_f32(_lib.ptr(x), _lib.ptr(U), _lib.ptr(y), B, H, W, cin, cout, _lib.ptr(bias),
-                                                _lib.ptr(scale), _lib.ptr(shift), None, 1 if relu else 0, _lib.ptr(part), part.numel() * 4 if bn_stats else 0,
-                                                ctypes.addressof(ns), _lib.stream_of(x)), "ud_conv3x3_wino_nhwc_f32")
+        _lib.ud.ud_conv3x3_wino_nhwc_f32(x, U, y, B, H, W, cin, cout, bias, scale, shift, None, 1 if relu else 0, part,
+                                         part.numel() * 4 if bn_stats else 0, ctypes.addressof(ns), _lib.stream_of(x))
         return (y, (part, ns.value, B * H * W)) if bn_stats else y
     w = weight.detach()
     w_tap = (w.permute(1, 2, 3, 0) if transposed else w.permute(0, 2, 3, 1)).contiguous()   # [n, 3, 3, c]; transposed: taps walked in reverse
     if bn_stats:      # + per-tile (sum, sum of squares) for the BatchNorm that follows: (y, (partial, slices, rows))
         part, ns = _bn_partial(lib.ud_conv3x3_bnstats_bytes(B, H, W, cout), x.device)
-        _lib.check(lib.ud_conv3x3_bnstats_nhwc_f32(_lib.ptr(x), _lib.ptr(w_tap), _lib.ptr(y), B, H, W, cin, cout,
-                                                   _lib.ptr(bias), _lib.ptr(part), part.numel() * 4,
-                                                   ctypes.addressof(ns), _lib.stream_of(x)),
-                   "ud_conv3x3_bnstats_nhwc_f32")
+        _lib.ud.ud_conv3x3_bnstats_nhwc_f32(x, w_tap, y, B, H, W, cin, cout, bias, part, part.numel() * 4, ctypes.addressof(ns),
+                                            _lib.stream_of(x))
         return y, (part, ns.value, B * H * W)
-    _lib.check(lib.ud_conv3x3_nhwc_f32(_lib.ptr(x), _lib.ptr(w_tap), _lib.ptr(y), B, H, W, cin, cout,
-                                       _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(shift), None,
-                                       (1 if relu else 0) | (2 if transposed else 0), _lib.stream_of(x)),
-               "ud_conv3x3_nhwc_f32")
+    _lib.ud.ud_conv3x3_nhwc_f32(x, w_tap, y, B, H, W, cin, cout, bias, scale, shift, None,
+                                (1 if relu else 0) | (2 if transposed else 0), _lib.stream_of(x))
     return y
 
 
@@ -208,10 +200,9 @@ def launch_1x1p(x, w, y, P, K, N, bias=None, residual=None, part=None, imap=None
     lib = _lib.load()
     ws = _lib.workspace(x.device, lib.ud_conv1x1p_f32_workspace_bytes(), "conv_1x1p")
     ns = ctypes.c_int(0)
-    _lib.check(lib.ud_conv1x1p_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), P, K, N, _lib.ptr(bias), None, None,
-                                        _lib.ptr(residual), 0, _lib.ptr(part), part.numel() * 4 if part is not None else 0,
-                                        ctypes.addressof(ns), imap, omap, x.numel(), y.numel(), _lib.ptr(ws), ws.numel(),
-                                        _lib.stream_of(x)), "ud_conv1x1p_nhwc_f32")
+    _lib.ud.ud_conv1x1p_nhwc_f32(x, w, y, P, K, N, bias, None, None, residual, 0, part,
+                                 part.numel() * 4 if part is not None else 0, ctypes.addressof(ns), imap, omap, x.numel(),
+                                 y.numel(), ws, ws.numel(), _lib.stream_of(x))
     return ns.value
 
 
@@ -235,14 +226,10 @@ def _launch1(x, w, cout, bias=None, residual=None, bn_stats=False):
     if bn_stats:
         lib = _lib.load()
         part, ns = _bn_partial(lib.ud_conv1x1_bnstats_bytes(B * H * W, cout), x.device)
-        _lib.check(lib.ud_conv1x1_bnstats_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), B * H * W, cin, cout,
-                                                   _lib.ptr(bias), _lib.ptr(part), part.numel() * 4,
-                                                   ctypes.addressof(ns), _lib.stream_of(x)),
-                   "ud_conv1x1_bnstats_nhwc_f32")
+        _lib.ud.ud_conv1x1_bnstats_nhwc_f32(x, w, y, B * H * W, cin, cout, bias, part, part.numel() * 4, ctypes.addressof(ns),
+                                            _lib.stream_of(x))
         return y, (part, ns.value, B * H * W)
-    _lib.check(_lib.load().ud_conv1x1_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), B * H * W, cin, cout,
-                                               _lib.ptr(bias), None, None, _lib.ptr(residual), 0, _lib.stream_of(x)),
-               "ud_conv1x1_nhwc_f32")
+    _lib.ud.ud_conv1x1_nhwc_f32(x, w, y, B * H * W, cin, cout, bias, None, None, residual, 0, _lib.stream_of(x))
     return y
 
 
@@ -272,15 +259,13 @@ def weight_grad(x, gy, w, ks):
         if wino and wino4_wgrad_pays(B, H, W, cin, cout):
             ws = _lib.workspace(x.device, lib.ud_conv3x3_wino4_wgrad_f32_workspace_bytes(B, H, W, cin, cout), "conv_wgrad")
             dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device)
-            _lib.check(lib.ud_conv3x3_wino4_wgrad_nhwc_f32(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), B, H, W, cin, cout, _lib.ptr(ws),
-                                                           ws.numel(), _lib.stream_of(x)), "ud_conv3x3_wino4_wgrad_nhwc_f32")
+            _lib.ud.ud_conv3x3_wino4_wgrad_nhwc_f32(x, gy, dw, B, H, W, cin, cout, ws, ws.numel(), _lib.stream_of(x))
             return dw.permute(0, 3, 1, 2)
-        nbytes, fn = ((lib.ud_conv3x3_wino_wgrad_f32_workspace_bytes, lib.ud_conv3x3_wino_wgrad_nhwc_f32) if wino else
-                      (lib.ud_conv3x3_wgrad_f32_workspace_bytes, lib.ud_conv3x3_wgrad_nhwc_f32))
+        nbytes, fn = ((lib.ud_conv3x3_wino_wgrad_f32_workspace_bytes, _lib.ud.ud_conv3x3_wino_wgrad_nhwc_f32) if wino else
+                      (lib.ud_conv3x3_wgrad_f32_workspace_bytes, _lib.ud.ud_conv3x3_wgrad_nhwc_f32))
         ws = _lib.workspace(x.device, nbytes(B, H, W, cin, cout), "conv_wgrad")
         dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device)
-        _lib.check(fn(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), B, H, W, cin, cout, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
-                   "ud_conv3x3_wino_wgrad_nhwc_f32" if wino else "ud_conv3x3_wgrad_nhwc_f32")
+        fn(x, gy, dw, B, H, W, cin, cout, ws, ws.numel(), _lib.stream_of(x))
         return dw.permute(0, 3, 1, 2)
     return wgrad_mapped(x, gy, B * H * W, cin, cout, None, None).view(cout, cin, 1, 1)
 
@@ -290,9 +275,7 @@ def wgrad_mapped(x, gy, P, K, N, xmap, ymap):
     lib = _lib.load()
     ws = _lib.workspace(x.device, lib.ud_conv1x1_wgrad_f32_workspace_bytes(P, K, N), "conv_wgrad")
     dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    _lib.check(lib.ud_conv1x1_wgrad_mapped_nhwc_f32(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(dw), P, K, N, xmap, ymap,
-                                                    _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
-               "ud_conv1x1_wgrad_mapped_nhwc_f32")
+    _lib.ud.ud_conv1x1_wgrad_mapped_nhwc_f32(x, gy, dw, P, K, N, xmap, ymap, ws, ws.numel(), _lib.stream_of(x))
     return dw
 
 

@@ -34,10 +34,8 @@ def lidar_depth_labels(points, sensor2ego, intrin, ida, bda, d_bound, final_dim,
     label = torch.empty((B, ncam, H // ds, W // ds), dtype=torch.int32, device=dev)
     lib = _lib.load()
     ws = _lib.workspace(dev, lib.ud_depth_labels_workspace_bytes(B, ncam), "depth_labels")
-    _lib.check(lib.ud_depth_labels(_lib.ptr(pts) if pts.shape[1] > 0 else None, pts.stride(0), pts.stride(1), B, pts.shape[1],
-                                   _lib.ptr(s2e), _lib.ptr(k), _lib.ptr(a), _lib.ptr(bd), ncam, H, W, ds, lo, hi, step, D,
-                                   _lib.ptr(dmin), _lib.ptr(label), _lib.ptr(ws), ws.numel(), _lib.stream_of(dmin)),
-               "ud_depth_labels")
+    _lib.ud.ud_depth_labels(pts if pts.shape[1] > 0 else None, pts.stride(0), pts.stride(1), B, pts.shape[1], s2e, k, a, bd,
+                            ncam, H, W, ds, lo, hi, step, D, dmin, label, ws, ws.numel(), _lib.stream_of(dmin))
     return dmin, label
 
 
@@ -56,8 +54,7 @@ class DepthLoss(torch.autograd.Function):
         res = torch.empty(2, dtype=torch.float32, device=logits.device)
         ws = _lib.workspace(logits.device, lib.ud_depth_loss_workspace_bytes(BN, fH, fW), "depth_loss")
         sn, sc, sh, sw = logits.stride()
-        _lib.check(lib.ud_depth_loss_fwd(_lib.ptr(logits), sn, sc, sh, sw, _lib.ptr(label), BN, D, fH, fW, _lib.ptr(res),
-                                         _lib.ptr(ws), ws.numel(), _lib.stream_of(logits)), "ud_depth_loss_fwd")
+        _lib.ud.ud_depth_loss_fwd(logits, sn, sc, sh, sw, label, BN, D, fH, fW, res, ws, ws.numel(), _lib.stream_of(logits))
         ctx.save_for_backward(logits, label)
         ctx.res = res
         return res[0]
@@ -70,9 +67,8 @@ class DepthLoss(torch.autograd.Function):
         dx = torch.empty_like(logits)                    # the logits' own axis order, dense
         sn, sc, sh, sw = logits.stride()
         dn, dc, dh, dw = dx.stride()
-        _lib.check(_lib.load().ud_depth_loss_bwd(_lib.ptr(logits), sn, sc, sh, sw, _lib.ptr(label), _lib.ptr(ctx.res),
-                                                 _lib.ptr(g), _lib.ptr(dx), dn, dc, dh, dw, BN, D, fH, fW,
-                                                 _lib.stream_of(dx)), "ud_depth_loss_bwd")
+        _lib.ud.ud_depth_loss_bwd(logits, sn, sc, sh, sw, label, ctx.res, g, dx, dn, dc, dh, dw, BN, D, fH, fW,
+                                  _lib.stream_of(dx))
         return dx, None
 
 

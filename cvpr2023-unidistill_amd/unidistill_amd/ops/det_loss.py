@@ -55,10 +55,9 @@ class _FocalFn(torch.autograd.Function):
         prob = torch.empty((T, B, ncm, H, W), dtype=torch.float32, device=gt.device)
         pos_neg = torch.empty((T, 2), dtype=torch.float32, device=gt.device)
         ws = _lib.workspace(gt.device, lib.ud_det_loss_workspace_bytes(T), "det_loss")
-        _lib.check(lib.ud_det_focal_fwd(_ptr_table(hms), (ctypes.c_longlong * T)(*[h.stride(0) for h in hms]),
-                                        (ctypes.c_int * T)(*ncls), T, B, ncm, H * W, _lib.ptr(gt), float(alpha),
-                                        float(gamma), _lib.ptr(prob), _lib.ptr(pos_neg), _lib.ptr(ws),
-                                        ws.numel(), _lib.stream_of(gt)), "ud_det_focal_fwd")
+        _lib.ud.ud_det_focal_fwd(_ptr_table(hms), (ctypes.c_longlong * T)(*[h.stride(0) for h in hms]),
+                                 (ctypes.c_int * T)(*ncls), T, B, ncm, H * W, gt, float(alpha), float(gamma), prob, pos_neg, ws,
+                                 ws.numel(), _lib.stream_of(gt))
         ctx.save_for_backward(gt, prob)
         ctx.cfg = (ncls, float(alpha), float(gamma))
         return prob, pos_neg[:, 0], pos_neg[:, 1]
@@ -70,10 +69,8 @@ class _FocalFn(torch.autograd.Function):
         T, B, ncm, H, W = prob.shape
         dl = torch.empty_like(prob)
         gp = None if g_prob is None else g_prob.contiguous().float()
-        _lib.check(_lib.load().ud_det_focal_bwd((ctypes.c_int * T)(*ncls), T, B, ncm, H * W, _lib.ptr(gt),
-                                                _lib.ptr(prob), _lib.ptr(gp), _lib.ptr(g_pos.contiguous().float()),
-                                                _lib.ptr(g_neg.contiguous().float()), alpha, gamma, _lib.ptr(dl),
-                                                _lib.stream_of(prob)), "ud_det_focal_bwd")
+        _lib.ud.ud_det_focal_bwd((ctypes.c_int * T)(*ncls), T, B, ncm, H * W, gt, prob, gp, g_pos.contiguous().float(),
+                                 g_neg.contiguous().float(), alpha, gamma, dl, _lib.stream_of(prob))
         return (None, None, None) + tuple(dl[t, :, :ncls[t]] for t in range(T))
 
 
@@ -109,10 +106,8 @@ class _RegFn(torch.autograd.Function):
         loc = torch.empty((T, B, K, ctx._forward_cls.LOC), dtype=torch.float32, device=dev)
         ws = _lib.workspace(dev, lib.ud_det_loss_workspace_bytes(T), "det_loss")
         fwd = ctx._forward_cls.FWD
-        _lib.check(getattr(lib, fwd)(table, (ctypes.c_longlong * len(strides))(*strides), T, B, K, H * W, nb,
-                                     _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(tgt), tgt.shape[-1],
-                                     _lib.ptr(num_obj), float(sx), float(sy), _lib.ptr(losses), _lib.ptr(loc),
-                                     _lib.ptr(ws), ws.numel(), _lib.stream_of(ind)), fwd)
+        getattr(_lib.ud, fwd)(table, (ctypes.c_longlong * len(strides))(*strides), T, B, K, H * W, nb, ind, mask_u8, tgt,
+                              tgt.shape[-1], num_obj, float(sx), float(sy), losses, loc, ws, ws.numel(), _lib.stream_of(ind))
         ctx.save_for_backward(ind, mask_u8, loc)
         ctx.cfg = (T, B, K, H, W, nb)
         return losses[:, :10], losses[:, 10], losses[:, 11]
@@ -124,9 +119,8 @@ class _RegFn(torch.autograd.Function):
         dhead = torch.zeros((T, B, 11, H, W), dtype=torch.float32, device=ind.device)
         z = lambda g, shape: (torch.zeros(shape, device=ind.device) if g is None else g.contiguous().float())
         bwd = ctx._forward_cls.BWD
-        _lib.check(getattr(_lib.load(), bwd)(T, B, K, H * W, nb, _lib.ptr(ind), _lib.ptr(mask_u8), _lib.ptr(loc),
-                                             _lib.ptr(z(g_box, (T, 10))), _lib.ptr(z(g_iou, (T,))),
-                                             _lib.ptr(z(g_aw, (T,))), _lib.ptr(dhead), _lib.stream_of(ind)), bwd)
+        getattr(_lib.ud, bwd)(T, B, K, H * W, nb, ind, mask_u8, loc, z(g_box, (T, 10)), z(g_iou, (T,)), z(g_aw, (T,)), dhead,
+                              _lib.stream_of(ind))
         grads = []
         for t in range(T):
             c = 0
@@ -160,8 +154,7 @@ class _RotIou3dFn(torch.autograd.Function):
         n = a.shape[0]
         iou = torch.empty((n,), dtype=torch.float32, device=a.device)
         diou = torch.empty((n, 7), dtype=torch.float32, device=a.device) if ctx.needs_input_grad[0] else None
-        _lib.check(_lib.load().ud_rot_iou3d_pairs(_lib.ptr(a), _lib.ptr(b), n, _lib.ptr(iou), _lib.ptr(diou),
-                                                  _lib.stream_of(a)), "ud_rot_iou3d_pairs")
+        _lib.ud.ud_rot_iou3d_pairs(a, b, n, iou, diou, _lib.stream_of(a))
         if diou is not None:
             ctx.save_for_backward(diou)
         return iou

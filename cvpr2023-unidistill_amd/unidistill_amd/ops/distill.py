@@ -31,10 +31,8 @@ def box_corners_bev(gt_boxes, pc_range, voxel_size, out_size_scale):
     B, M, S = gt.shape
     corners = torch.empty((B, M, 4, 2), dtype=torch.float32, device=gt.device)
     valid = torch.empty((B, M), dtype=torch.uint8, device=gt.device)
-    _lib.check(_lib.load().ud_distill_box_corners(
-        _lib.ptr(gt), B, M, S, float(pc_range[0]), float(pc_range[1]),
-        float(voxel_size[0] * out_size_scale), float(voxel_size[1] * out_size_scale),
-        _lib.ptr(corners), _lib.ptr(valid), _lib.stream_of(gt)), "ud_distill_box_corners")
+    _lib.ud.ud_distill_box_corners(gt, B, M, S, float(pc_range[0]), float(pc_range[1]), float(voxel_size[0] * out_size_scale),
+                                   float(voxel_size[1] * out_size_scale), corners, valid, _lib.stream_of(gt))
     return corners, valid.bool()
 
 
@@ -85,9 +83,8 @@ class _FeatureTap(torch.autograd.Function):
             B, C, H, W = sx.shape
             M = corners.shape[1]
             ws = _lib.workspace(sx.device, lib.ud_distill_box_bwd_workspace_bytes(B, M, C), "distill_bwd")
-            _lib.check(lib.ud_distill_box_bwd_acc(kind, _lib.ptr(sx), _strides(sx), _lib.ptr(tx), _strides(tx), _lib.ptr(corners),
-                                                  _lib.ptr(valid_u8), B, M, C, H, W, _lib.ptr(gscale), _lib.ptr(g), _strides(g),
-                                                  _lib.ptr(ws), ws.numel(), _lib.stream_of(sx)), "ud_distill_box_bwd_acc")
+            _lib.ud.ud_distill_box_bwd_acc(kind, sx, _strides(sx), tx, _strides(tx), corners, valid_u8, B, M, C, H, W, gscale,
+                                           g, _strides(g), ws, ws.numel(), _lib.stream_of(sx))
         return g, None
 
 
@@ -126,10 +123,8 @@ class _BoxDistill(torch.autograd.Function):
         B, C, H, W = s.shape
         M = corners.shape[1]
         box_loss = torch.empty((B, M), dtype=torch.float32, device=s.device)
-        _lib.check(_lib.load().ud_distill_box_fwd(kind, _lib.ptr(s), _strides(s), _lib.ptr(t),
-                                                  _strides(t), _lib.ptr(corners), _lib.ptr(valid_u8),
-                                                  B, M, C, H, W, _lib.ptr(box_loss),
-                                                  _lib.stream_of(s)), "ud_distill_box_fwd")
+        _lib.ud.ud_distill_box_fwd(kind, s, _strides(s), t, _strides(t), corners, valid_u8, B, M, C, H, W, box_loss,
+                                   _lib.stream_of(s))
         den = weight + 1e-4
         ctx.save_for_backward(s, t, corners, valid_u8, den)
         ctx.kind = kind
@@ -149,11 +144,8 @@ class _BoxDistill(torch.autograd.Function):
         gs = torch.zeros_like(s)
         lib = _lib.load()
         ws = _lib.workspace(s.device, lib.ud_distill_box_bwd_workspace_bytes(B, M, C), "distill_bwd")
-        _lib.check(lib.ud_distill_box_bwd(ctx.kind, _lib.ptr(s), _strides(s), _lib.ptr(t),
-                                          _strides(t), _lib.ptr(corners), _lib.ptr(valid_u8),
-                                          B, M, C, H, W, _lib.ptr(gscale), _lib.ptr(gs),
-                                          _strides(gs), _lib.ptr(ws), ws.numel(), _lib.stream_of(s)),
-                   "ud_distill_box_bwd")
+        _lib.ud.ud_distill_box_bwd(ctx.kind, s, _strides(s), t, _strides(t), corners, valid_u8, B, M, C, H, W, gscale, gs,
+                                   _strides(gs), ws, ws.numel(), _lib.stream_of(s))
         return None, gs, None, None, None, None, None
 
 
@@ -183,10 +175,8 @@ def calculate_box_mask_gaussian(preds_shape, target, pc_range, voxel_size, out_s
     lib = _lib.load()
     mask = torch.empty((B, H, W), dtype=torch.float32, device=gt.device)
     ws = _lib.workspace(gt.device, lib.ud_distill_mask_workspace_bytes(B, M), "distill_mask")
-    _lib.check(lib.ud_distill_gaussian_mask(
-        _lib.ptr(gt), B, M, S, float(pc_range[0]), float(pc_range[1]),
-        float(voxel_size[0] * out_size_scale), float(voxel_size[1] * out_size_scale), H, W,
-        _lib.ptr(mask), _lib.ptr(ws), ws.numel(), _lib.stream_of(gt)), "ud_distill_gaussian_mask")
+    _lib.ud.ud_distill_gaussian_mask(gt, B, M, S, float(pc_range[0]), float(pc_range[1]), float(voxel_size[0] * out_size_scale),
+                                     float(voxel_size[1] * out_size_scale), H, W, mask, ws, ws.numel(), _lib.stream_of(gt))
     return mask
 
 
@@ -224,11 +214,10 @@ class _RespDistill(torch.autograd.Function):
         reg_ch = (ctypes.c_int * n_reg)(*[t.shape[1] for t in s_reg])
         nblk = B * ((H * W + 255) // 256)
         partial = torch.empty((nblk, 2), dtype=torch.float32, device=mask.device)
-        _lib.check(_lib.load().ud_distill_resp_fwd_strided(
-            _ptr_array(s_hm), _stride_array(s_hm), _ptr_array(t_hm), _stride_array(t_hm), hm_ch, n_hm,
-            _ptr_array(s_reg), _stride_array(s_reg), _ptr_array(t_reg), _stride_array(t_reg), reg_ch, n_reg,
-            _lib.ptr(mask), B, H, W, float(clamp), float(1.0 - clamp), _lib.ptr(partial), _lib.stream_of(mask)),
-            "ud_distill_resp_fwd_strided")
+        _lib.ud.ud_distill_resp_fwd_strided(_ptr_array(s_hm), _stride_array(s_hm), _ptr_array(t_hm), _stride_array(t_hm), hm_ch,
+                                            n_hm, _ptr_array(s_reg), _stride_array(s_reg), _ptr_array(t_reg),
+                                            _stride_array(t_reg), reg_ch, n_reg, mask, B, H, W, float(clamp),
+                                            float(1.0 - clamp), partial, _lib.stream_of(mask))
         den = weight + 1e-4
         sums = partial.sum(0)
         ctx.save_for_backward(mask, den, *s_hm, *s_reg, *t_hm, *t_reg)
@@ -256,11 +245,11 @@ class _RespDistill(torch.autograd.Function):
         sr = (g_reg / den).reshape(1).float().contiguous()
         hm_ch = (ctypes.c_int * n_hm)(*[t.shape[1] for t in s_hm])
         reg_ch = (ctypes.c_int * n_reg)(*[t.shape[1] for t in s_reg])
-        _lib.check(_lib.load().ud_distill_resp_bwd_strided(
-            _ptr_array(s_hm), _stride_array(s_hm), _ptr_array(t_hm), _stride_array(t_hm), _ptr_array(gh), _stride_array(gh),
-            hm_ch, n_hm, _ptr_array(s_reg), _stride_array(s_reg), _ptr_array(t_reg), _stride_array(t_reg), _ptr_array(gr),
-            _stride_array(gr), reg_ch, n_reg, _lib.ptr(mask), B, H, W, float(clamp), float(1.0 - clamp), _lib.ptr(sc),
-            _lib.ptr(sr), _lib.stream_of(mask)), "ud_distill_resp_bwd_strided")
+        _lib.ud.ud_distill_resp_bwd_strided(_ptr_array(s_hm), _stride_array(s_hm), _ptr_array(t_hm), _stride_array(t_hm),
+                                            _ptr_array(gh), _stride_array(gh), hm_ch, n_hm, _ptr_array(s_reg),
+                                            _stride_array(s_reg), _ptr_array(t_reg), _stride_array(t_reg), _ptr_array(gr),
+                                            _stride_array(gr), reg_ch, n_reg, mask, B, H, W, float(clamp), float(1.0 - clamp),
+                                            sc, sr, _lib.stream_of(mask))
         return (None, None, None, None, *gh, *gr, *([None] * (n_hm + n_reg)))
 
 

@@ -47,10 +47,8 @@ class _HeadTailFn(torch.autograd.Function):
             mean, var, invstd, scale, shift = vec[0], vec[1], vec[2], vec[3], vec[4]
             fp32_buffers = running_mean is not None and running_mean.dtype == torch.float32
             rm, rv = (running_mean, running_var) if fp32_buffers else (None, None)   # updated in-kernel
-            _lib.check(lib.ud_head_tail_stats(_lib.ptr(y), B, H, W, G, _lib.ptr(g32), _lib.ptr(b32),
-                                              float(eps), _lib.ptr(mean), _lib.ptr(var),
-                                              _lib.ptr(invstd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rm), _lib.ptr(rv),
-                                              float(momentum or 0.0), None, _lib.ptr(ws), ws.numel(), stream), "ud_head_tail_stats")
+            _lib.ud.ud_head_tail_stats(y, B, H, W, G, g32, b32, float(eps), mean, var, invstd, scale, shift, rm, rv,
+                                       float(momentum or 0.0), None, ws, ws.numel(), stream)
             if rm is not None:            # written through raw pointers by the kernel: move the version counters
                 torch.autograd.graph.increment_version(rm)
                 torch.autograd.graph.increment_version(rv)
@@ -65,9 +63,7 @@ class _HeadTailFn(torch.autograd.Function):
             scale = (g32 * invstd).contiguous()
             shift = (b32 - mean * scale).contiguous()
         z = torch.empty((B, G * kmax, H, W), dtype=torch.float32, device=dev)
-        _lib.check(lib.ud_head_tail_fwd(_lib.ptr(y), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(wk),
-                                        _lib.ptr(b2.detach().float().contiguous()), _lib.ptr(z),
-                                        B, H, W, G, kmax, stream), "ud_head_tail_fwd")
+        _lib.ud.ud_head_tail_fwd(y, scale, shift, wk, b2.detach().float().contiguous(), z, B, H, W, G, kmax, stream)
         ctx.save_for_backward(y, wk, scale, shift, mean, invstd)
         ctx.cfg = (bool(training), G, kmax, w2.shape)
         return z
@@ -86,11 +82,8 @@ class _HeadTailFn(torch.autograd.Function):
         dwk = torch.empty_like(wk)
         dgb = torch.empty((2, C), dtype=torch.float32, device=y.device)
         ws = _lib.workspace(y.device, lib.ud_head_tail_workspace_bytes(G), "head_tail")
-        _lib.check(lib.ud_head_tail_bwd(_lib.ptr(y), _lib.ptr(dz), _lib.ptr(wk), _lib.ptr(scale),
-                                        _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(dy),
-                                        _lib.ptr(dwk), _lib.ptr(dgb[0]), _lib.ptr(dgb[1]), B, H, W, G,
-                                        kmax, _lib.ptr(ws), ws.numel(), _lib.stream_of(y)),
-                   "ud_head_tail_bwd")
+        _lib.ud.ud_head_tail_bwd(y, dz, wk, scale, shift, mean, invstd, dy, dwk, dgb[0], dgb[1], B, H, W, G, kmax, ws,
+                                 ws.numel(), _lib.stream_of(y))
         dw2 = dwk.permute(0, 1, 3, 2).reshape(wshape)
         db2 = dz.sum((0, 2, 3))
         return dy, dgb[0], dgb[1], dw2, db2, None, None, None, None, None, None, None

@@ -25,8 +25,7 @@ class _GroupTail(torch.autograd.Function):
         wt = weight.detach().permute(0, 2, 3, 1).contiguous()          # [G*KM, 3, 3, 64] = [G][KM][9][64]
         z = torch.empty((B, G * KM, H, W), dtype=torch.float32, device=a.device, memory_format=torch.channels_last)
         b = None if bias is None else bias.detach().contiguous()
-        _lib.check(_lib.load().ud_head_tail_f32_fwd(_lib.ptr(a), _lib.ptr(wt), _lib.ptr(b), _lib.ptr(z), B, H, W, G,
-                                                    KM, _lib.stream_of(a)), "ud_head_tail_f32_fwd")
+        _lib.ud.ud_head_tail_f32_fwd(a, wt, b, z, B, H, W, G, KM, _lib.stream_of(a))
         ctx.save_for_backward(a, wt)
         ctx.cfg = (G, KM, bias is not None)
         return z
@@ -43,14 +42,12 @@ class _GroupTail(torch.autograd.Function):
         st = _lib.stream_of(a)
         if ctx.needs_input_grad[0]:
             da = torch.empty_like(a)
-            _lib.check(lib.ud_head_tail_f32_dgrad(_lib.ptr(dz), _lib.ptr(wt), _lib.ptr(da), B, H, W, G, KM, st),
-                       "ud_head_tail_f32_dgrad")
+            _lib.ud.ud_head_tail_f32_dgrad(dz, wt, da, B, H, W, G, KM, st)
         if ctx.needs_input_grad[1]:
             need = lib.ud_head_tail_f32_wgrad_workspace_bytes(B, H, W, G, KM)
             ws = _lib.workspace(a.device, need, "head_tail_f32")
             dwt = torch.empty((G * KM, 3, 3, 64), dtype=torch.float32, device=a.device)
-            _lib.check(lib.ud_head_tail_f32_wgrad(_lib.ptr(a), _lib.ptr(dz), _lib.ptr(dwt), B, H, W, G, KM,
-                                                  _lib.ptr(ws), ws.numel(), st), "ud_head_tail_f32_wgrad")
+            _lib.ud.ud_head_tail_f32_wgrad(a, dz, dwt, B, H, W, G, KM, ws, ws.numel(), st)
             dw = dwt.permute(0, 3, 1, 2)
         if has_bias and ctx.needs_input_grad[2]:
             db = bn_act.bias_grad(dz)
@@ -82,9 +79,7 @@ class _BnReluGroupTail(torch.autograd.Function):
         wt = weight.detach().permute(0, 2, 3, 1).contiguous()          # [G*KM, 3, 3, 64] = [G][KM][9][64]
         z = torch.empty((B, G * KM, H, W), dtype=torch.float32, device=y.device, memory_format=torch.channels_last)
         b = None if bias is None else bias.detach().contiguous()
-        _lib.check(_lib.load().ud_head_tail_f32_bn_fwd(_lib.ptr(y), v0 + 3 * row, v0 + 4 * row, _lib.ptr(wt), _lib.ptr(b),
-                                                       _lib.ptr(z), B, H, W, G, KM, _lib.stream_of(y)),
-                   "ud_head_tail_f32_bn_fwd")
+        _lib.ud.ud_head_tail_f32_bn_fwd(y, v0 + 3 * row, v0 + 4 * row, wt, b, z, B, H, W, G, KM, _lib.stream_of(y))
         ctx.save_for_backward(y, vec, wt)
         ctx.cfg = (G, KM, bias is not None, bool(training))
         ctx.weight_param = weight
@@ -109,9 +104,8 @@ class _BnReluGroupTail(torch.autograd.Function):
                 need = lib.ud_head_tail_f32_wgrad_workspace_bytes(B, H, W, G, KM)
                 ws = _lib.workspace(y.device, need, "head_tail_f32")
                 dwt = torch.empty((G * KM, 3, 3, 64), dtype=torch.float32, device=y.device)
-                _lib.check(lib.ud_head_tail_f32_bn_wgrad(_lib.ptr(y), v0 + 3 * row, v0 + 4 * row, _lib.ptr(dz), _lib.ptr(dwt), B, H, W,
-                                                         G, KM, _lib.ptr(ws), ws.numel(), _lib.stream_of(y)),
-                           "ud_head_tail_f32_bn_wgrad")
+                _lib.ud.ud_head_tail_f32_bn_wgrad(y, v0 + 3 * row, v0 + 4 * row, dz, dwt, B, H, W, G, KM, ws, ws.numel(),
+                                                  _lib.stream_of(y))
                 return dwt.permute(0, 3, 1, 2)
             # (reads y and dz only: beside the BatchNorm-backward passes below on the weight-gradient stream, ops/wgrad_stream.py)
             dw = wgrad_stream.defer(ctx.weight_param, wgrad, y, dz, vec) if os.environ.get("UD_TAIL_WGRAD_STREAM", "1") == "1" else wgrad()
@@ -124,19 +118,16 @@ class _BnReluGroupTail(torch.autograd.Function):
                 # + the per-channel sums of dy from the pass that stores it: the bias gradient of the first convolution
                 # (center_head.py:339: bias=True in front of the BatchNorm) without another pass over the 1.39 GB gradient
                 colsum = torch.empty(C, dtype=torch.float32, device=y.device) if EMIT_COLSUM else None
-                _lib.check(lib.ud_head_tail_f32_bn_bwd(_lib.ptr(dz), _lib.ptr(wt), y.data_ptr(), v0 + 3 * row, v0 + 4 * row, v0,
-                                                       v0 + 2 * row, dy.data_ptr(), g0, g0 + row, _lib.ptr(colsum), B, H, W, G, KM,
-                                                       _lib.ptr(bws), bws.numel(), st), "ud_head_tail_f32_bn_bwd")
+                _lib.ud.ud_head_tail_f32_bn_bwd(dz, wt, y.data_ptr(), v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row,
+                                                dy.data_ptr(), g0, g0 + row, colsum, B, H, W, G, KM, bws, bws.numel(), st)
                 if colsum is not None:
                     bn_act.attach_colsum(dy, colsum)
             else:
                 da = torch.empty_like(y)                     # gradient at relu(bn(y))
-                _lib.check(lib.ud_head_tail_f32_dgrad(_lib.ptr(dz), _lib.ptr(wt), _lib.ptr(da), B, H, W, G, KM, st),
-                           "ud_head_tail_f32_dgrad")
+                _lib.ud.ud_head_tail_f32_dgrad(dz, wt, da, B, H, W, G, KM, st)
                 bws = bn_act._workspace(y.device, C)
-                _lib.check(lib.ud_bn_act_bwd_f32(y.data_ptr(), None, da.data_ptr(), v0 + 3 * row, v0 + 4 * row, v0,
-                                                 v0 + 2 * row, dy.data_ptr(), None, g0, g0 + row, P, C, 1, bws.data_ptr(),
-                                                 bws.numel(), st), "ud_bn_act_bwd")
+                _lib.ud.ud_bn_act_bwd_f32(y.data_ptr(), None, da.data_ptr(), v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row,
+                                          dy.data_ptr(), None, g0, g0 + row, P, C, 1, bws.data_ptr(), bws.numel(), st)
             dgamma, dbeta = dgb[0], dgb[1]
         if has_bias and ctx.needs_input_grad[11]:
             db = bn_act.bias_grad(dz)

@@ -30,9 +30,7 @@ def points_transform(points, seg, mats, last=None, out=None):
     last_d = None if last is None else torch.as_tensor(np.asarray(last, np.float32).reshape(S), device=dev)
     out = torch.empty_like(points) if out is None else out
     max_rows = max((b - a for a, b in zip(seg, seg[1:])), default=0)
-    _lib.check(_lib.load().ud_points_transform(_lib.ptr(points), _lib.ptr(out), _lib.ptr(seg_d), _lib.ptr(mats_d),
-                                               _lib.ptr(last_d), S, points.shape[1], max_rows, _lib.stream_of(points)),
-               "ud_points_transform")
+    _lib.ud.ud_points_transform(points, out, seg_d, mats_d, last_d, S, points.shape[1], max_rows, _lib.stream_of(points))
     return out
 
 
@@ -119,9 +117,8 @@ def image_normalize(imgs_u8, mean=IMG_MEAN, std=IMG_STD, to_rgb=TO_RGB, channels
         out = torch.empty((NI, H, W, 3), dtype=torch.float32, device=x.device)
     else:
         out = torch.empty((NI, 3, H, W), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().ud_image_normalize(_lib.ptr(x), _lib.ptr(out), f3(mean), f3(std), 1 if to_rgb else 0,
-                                              NI, H, W, 1 if channels_last else 0, _lib.stream_of(x)),
-               "ud_image_normalize")
+    _lib.ud.ud_image_normalize(x, out, f3(mean), f3(std), 1 if to_rgb else 0, NI, H, W, 1 if channels_last else 0,
+                               _lib.stream_of(x))
     if channels_last:
         out = out.permute(0, 3, 1, 2)              # [NI, 3, H, W] view of the NHWC buffer
     return out.reshape(*lead, 3, H, W)             # only splits the leading axis: a view in both layouts
@@ -142,7 +139,7 @@ def _fill_batch_tensor(batch_data, device):
     import ctypes
     ptrs = (ctypes.c_void_p * B)(*[t.data_ptr() if t.numel() else None for t in dev_ts])
     rows = (ctypes.c_int64 * B)(*[n if t.numel() else 0 for n, t in zip(lens, dev_ts)])
-    _lib.check(_lib.load().ud_collate_pad(ptrs, rows, B, L, W, _lib.ptr(out), _lib.stream_of(out)), "ud_collate_pad")
+    _lib.ud.ud_collate_pad(ptrs, rows, B, L, W, out, _lib.stream_of(out))
     return out
 
 
@@ -505,9 +502,8 @@ def _affine_launch(img, img_bytes, H, W, row_stride, recs, final_dim, normalize,
         mode = 0
     import ctypes
     f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
-    _lib.check(lib.ud_image_affine(img, img_bytes, H, W, row_stride, recs.ctypes.data, _lib.ptr(recs_d), N, fH, fW,
-                                   mode, _lib.ptr(out), f3(mean), f3(std), 1 if to_rgb else 0, _lib.ptr(ws),
-                                   ws.numel(), _lib.stream_of(out)), "ud_image_affine")
+    _lib.ud.ud_image_affine(img, img_bytes, H, W, row_stride, recs.ctypes.data, recs_d, N, fH, fW, mode, out, f3(mean), f3(std),
+                            1 if to_rgb else 0, ws, ws.numel(), _lib.stream_of(out))
     if normalize and channels_last:
         out = out.permute(0, 3, 1, 2)              # [N, 3, fH, fW] view of the NHWC buffer
     return out
@@ -547,7 +543,7 @@ def image_affine(imgs_u8, augs, final_dim=(256, 704), normalize=True, mean=IMG_M
         recs[:, idx("src_row0")] = 0
         recs[:, idx("src_rows")] = H
     img_bytes = 1 + sum((n - 1) * s for n, s in zip(imgs_u8.shape, imgs_u8.stride()))
-    out = _affine_launch(_lib.ptr(imgs_u8), img_bytes, H, W, imgs_u8.stride(-3), recs, (fH, fW), normalize, mean, std,
+    out = _affine_launch(imgs_u8, img_bytes, H, W, imgs_u8.stride(-3), recs, (fH, fW), normalize, mean, std,
                          to_rgb, channels_last, imgs_u8.device)
     if normalize:
         out = out.reshape(*lead, 3, fH, fW)
@@ -591,7 +587,7 @@ def image_affine_host_frames(frames, augs, device, final_dim=(256, 704), **kw):
         recs[f, idx("src_off")], recs[f, idx("src_row0")], recs[f, idx("src_rows")] = off, b0, rows
         off += rows * row
     dev = host.to(device, non_blocking=True)
-    out = _affine_launch(_lib.ptr(dev), dev.numel(), H, W, row, recs, (fH, fW), kw.get("normalize", True),
+    out = _affine_launch(dev, dev.numel(), H, W, row, recs, (fH, fW), kw.get("normalize", True),
                          kw.get("mean", IMG_MEAN), kw.get("std", IMG_STD), kw.get("to_rgb", TO_RGB),
                          kw.get("channels_last", False), device)
     if kw.get("normalize", True):
@@ -659,7 +655,7 @@ def _lidar_run(pts_ptr, rows, D, parts, plan_base, device, stream, out_compact):
     counts_d = torch.empty(max(B, 1), dtype=torch.int64, device=device)
     hs = stream.cuda_stream
     args = (pts_ptr, rows, D, seg.ctypes.data, sseg.ctypes.data, S, B, p["seg"], p["sseg"], p["seg_par"], p["smp_par"])
-    _lib.check(lib.ud_lidar_prep_count(*args, _lib.ptr(counts_d), _lib.ptr(ws), ws_bytes, hs), "ud_lidar_prep_count")
+    _lib.ud.ud_lidar_prep_count(*args, counts_d, ws, ws_bytes, hs)
     counts_h = torch.empty(max(B, 1), dtype=torch.int64, pin_memory=True)
     counts_h.copy_(counts_d, non_blocking=True)
     ev = torch.cuda.Event()
@@ -672,8 +668,8 @@ def _lidar_run(pts_ptr, rows, D, parts, plan_base, device, stream, out_compact):
     else:
         out = torch.empty((B, nmax, D), dtype=torch.float32, device=device)
     out_rows = out.numel() // D
-    _lib.check(lib.ud_lidar_prep_compact(*args, counts.ctypes.data, _lib.ptr(counts_d), nmax, 1 if out_compact else 0,
-                                         _lib.ptr(out), out_rows, _lib.ptr(ws), ws_bytes, hs), "ud_lidar_prep_compact")
+    _lib.ud.ud_lidar_prep_compact(*args, counts.ctypes.data, counts_d, nmax, 1 if out_compact else 0, out, out_rows, ws,
+                                  ws_bytes, hs)
     return out, counts
 
 
@@ -695,7 +691,7 @@ def points_range_filter(points, point_cloud_range, seg=None):
     device = points.device
     plan = torch.from_numpy(buf).to(device)
     stream = torch.cuda.current_stream(device)
-    return _lidar_run(_lib.ptr(points), rows, D, parts, plan.data_ptr(), device, stream, True)
+    return _lidar_run(points, rows, D, parts, plan.data_ptr(), device, stream, True)
 
 
 def sweep_time_lag(info, sweep):

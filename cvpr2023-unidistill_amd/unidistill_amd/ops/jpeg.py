@@ -55,7 +55,7 @@ def parse(buf):
     rec = UdJpegFrame()
     rc = _lib.load().ud_jpeg_parse(data, len(data), ctypes.byref(rec))
     if rc < 0:
-        _lib.check(rc, "ud_jpeg_parse")
+        _lib.check(rc, "ud_jpeg_parse")  # raw handle: the positive codes go back to the caller, only a negative one is an error
     return rc, rec
 
 
@@ -170,9 +170,9 @@ def jpeg_decode(buffers, device, out=None):
             ws = _lib.workspace(device, ws_bytes, slot="jpeg")
             ws.record_stream(s)
             st_d = torch.empty(2 * len(recs), dtype=torch.int32, device=device)
-            _lib.check(lib.ud_jpeg_decode(dev.data_ptr(), src_bytes, rec_arr, dev.data_ptr() + rec_off, len(recs),
-                                          out.data_ptr(), out.numel(), st_d.data_ptr(), st_d.data_ptr() + 4 * len(recs),
-                                          ws.data_ptr(), ws.numel(), s.cuda_stream), "ud_jpeg_decode")
+            _lib.ud.ud_jpeg_decode(dev.data_ptr(), src_bytes, rec_arr, dev.data_ptr() + rec_off, len(recs), out.data_ptr(),
+                                   out.numel(), st_d.data_ptr(), st_d.data_ptr() + 4 * len(recs), ws.data_ptr(), ws.numel(),
+                                   s.cuda_stream)
             idx = torch.tensor([i for i, _ in recs], dtype=torch.int64).to(device, non_blocking=True)
             status.index_copy_(0, idx, st_d[:len(recs)])
             iters.index_copy_(0, idx, st_d[len(recs):])

@@ -35,9 +35,7 @@ def prepare_mats(sensor2ego, intrin, ida, bda, ida_inv=None, intrin_inv=None):
     s2e, k, a = (t.contiguous().float() for t in (sensor2ego, intrin, ida))
     bd, ai, ki = (None if t is None else t.contiguous().float() for t in (bda, ida_inv, intrin_inv))
     mats = torch.empty((B * ncam, 3, 16), dtype=torch.float32, device=s2e.device)
-    _lib.check(_lib.load().ud_lss_prepare_mats(_lib.ptr(s2e), _lib.ptr(k), _lib.ptr(a), _lib.ptr(bd),
-                                               _lib.ptr(ai), _lib.ptr(ki), B, ncam, _lib.ptr(mats),
-                                               _lib.stream_of(s2e)), "ud_lss_prepare_mats")
+    _lib.ud.ud_lss_prepare_mats(s2e, k, a, bd, ai, ki, B, ncam, mats, _lib.stream_of(s2e))
     return mats
 
 
@@ -47,10 +45,8 @@ def geometry(mats, fu, fv, fd, B, ncam, lo, size, has_bda=True, want_geom=False)
     dev = mats.device
     bins = torch.empty((B, ncam * D * fH * fW, 3), dtype=torch.int32, device=dev)
     geom = torch.empty((B, ncam, D, fH, fW, 3), dtype=torch.float32, device=dev) if want_geom else None
-    _lib.check(_lib.load().ud_lss_geometry(_lib.ptr(mats), _lib.ptr(fu), _lib.ptr(fv), _lib.ptr(fd),
-                                           B, ncam, D, fH, fW, _f3(lo), _f3(size), 1 if has_bda else 0,
-                                           _lib.ptr(geom), _lib.ptr(bins), _lib.stream_of(mats)),
-               "ud_lss_geometry")
+    _lib.ud.ud_lss_geometry(mats, fu, fv, fd, B, ncam, D, fH, fW, _f3(lo), _f3(size), 1 if has_bda else 0, geom, bins,
+                            _lib.stream_of(mats))
     return bins, geom
 
 
@@ -66,9 +62,7 @@ def depth_ctx(depth_feature, D, C):
         sn, sc, sh, sw = x.stride()
     prob = torch.empty((BN, D, fH * fW), dtype=torch.float32, device=x.device)
     ctx = torch.empty((BN, fH * fW, C), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().ud_lss_depth_ctx(_lib.ptr(x), sn, sc, sh, sw, BN, D, C, fH, fW,
-                                            _lib.ptr(prob), _lib.ptr(ctx), _lib.stream_of(x)),
-               "ud_lss_depth_ctx")
+    _lib.ud.ud_lss_depth_ctx(x, sn, sc, sh, sw, BN, D, C, fH, fW, prob, ctx, _lib.stream_of(x))
     return prob, ctx
 
 
@@ -97,9 +91,8 @@ def _lift_bwd(gsrc, pos, prob, ctx, like, ncam, D, C, nx, ny):
     lib = _lib.load()
     need = lib.ud_lss_lift_bwd_workspace_bytes(BN, D, C, fH, fW)
     ws = _lib.workspace(device, need, "lss_bwd")
-    _lib.check(lib.ud_lss_lift_bwd(_lib.ptr(gsrc), _lib.ptr(pos), _lib.ptr(prob), _lib.ptr(ctx),
-                                   _lib.ptr(g), sn, sc, sh, sw, BN, ncam, D, C, fH, fW, nx, ny,
-                                   _lib.ptr(ws), ws.numel(), _lib.stream_of(g)), "ud_lss_lift_bwd")
+    _lib.ud.ud_lss_lift_bwd(gsrc, pos, prob, ctx, g, sn, sc, sh, sw, BN, ncam, D, C, fH, fW, nx, ny, ws, ws.numel(),
+                            _lib.stream_of(g))
     return g
 
 
@@ -112,8 +105,7 @@ class Lift(torch.autograd.Function):
         prob, cpm = depth_ctx(depth_feature, D, C)
         BN, _, fH, fW = depth_feature.shape
         lifted = torch.empty((BN, D, fH, fW, C), dtype=torch.float32, device=depth_feature.device)
-        _lib.check(_lib.load().ud_lss_lift_fwd(_lib.ptr(prob), _lib.ptr(cpm), _lib.ptr(lifted), BN, D,
-                                               C, fH, fW, _lib.stream_of(lifted)), "ud_lss_lift_fwd")
+        _lib.ud.ud_lss_lift_fwd(prob, cpm, lifted, BN, D, C, fH, fW, _lib.stream_of(lifted))
         ctx.save_for_backward(prob, cpm)
         ctx.meta = ((tuple(depth_feature.shape), tuple(depth_feature.stride()), depth_feature.device), D, C)
         ctx.mark_non_differentiable()
@@ -153,16 +145,11 @@ class LiftSplat(torch.autograd.Function):
         if frustum is not None:
             mats, fu, fv, fd, lo, size, has_bda = frustum
             assert fd.numel() == D and fv.numel() == fH and fu.numel() == fW and mats.shape[0] == BN
-            _lib.check(lib.ud_lss_splat_geom_fwd(_lib.ptr(mats), _lib.ptr(fu), _lib.ptr(fv), _lib.ptr(fd), _f3(lo), _f3(size),
-                                                 1 if has_bda else 0, _lib.ptr(prob), _lib.ptr(cpm), _lib.ptr(out),
-                                                 _lib.ptr(pos), B, ncam, D, fH, fW, C, nx, ny, nz,
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_of(out)),
-                       "ud_lss_splat_geom_fwd")
+            _lib.ud.ud_lss_splat_geom_fwd(mats, fu, fv, fd, _f3(lo), _f3(size), 1 if has_bda else 0, prob, cpm, out, pos, B,
+                                          ncam, D, fH, fW, C, nx, ny, nz, ws, ws.numel(), _lib.stream_of(out))
         else:
-            _lib.check(lib.ud_lss_splat_fwd(_lib.ptr(bins), _lib.ptr(prob), _lib.ptr(cpm), _lib.ptr(out),
-                                            _lib.ptr(pos), B, ncam, D, fH, fW, C, nx, ny, nz,
-                                            _lib.ptr(ws), ws.numel(), _lib.stream_of(out)),
-                       "ud_lss_splat_fwd")
+            _lib.ud.ud_lss_splat_fwd(bins, prob, cpm, out, pos, B, ncam, D, fH, fW, C, nx, ny, nz, ws, ws.numel(),
+                                     _lib.stream_of(out))
         ctx.save_for_backward(prob, cpm, pos)
         ctx.meta = ((tuple(depth_feature.shape), tuple(depth_feature.stride()), depth_feature.device),
                     ncam, D, C, nx, ny)

@@ -19,8 +19,7 @@ def _run(boxes, thresh):
     keep = torch.empty((max(n, 1),), dtype=torch.int64, device=boxes.device)
     count = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
     ws = _lib.workspace(boxes.device, lib.ud_nms_bev_workspace_bytes(max(n, 1)), "nms")
-    _lib.check(lib.ud_nms_rotated_bev(_lib.ptr(boxes), n, float(thresh), _lib.ptr(keep), _lib.ptr(count),
-                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(boxes)), "ud_nms_rotated_bev")
+    _lib.ud.ud_nms_rotated_bev(boxes, n, float(thresh), keep, count, ws, ws.numel(), _lib.stream_of(boxes))
     return keep[:n], count
 
 
@@ -52,6 +51,5 @@ def boxes_iou_bev_gpu(boxes_a, boxes_b):
     _lib.require_gpu(boxes_a, boxes_b)
     a, b = boxes_a[:, :7].contiguous().float(), boxes_b[:, :7].contiguous().float()
     out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    _lib.check(_lib.load().ud_boxes_iou_bev(_lib.ptr(a), a.shape[0], _lib.ptr(b), b.shape[0], _lib.ptr(out),
-                                            _lib.stream_of(a)), "ud_boxes_iou_bev")
+    _lib.ud.ud_boxes_iou_bev(a, a.shape[0], b, b.shape[0], out, _lib.stream_of(a))
     return out

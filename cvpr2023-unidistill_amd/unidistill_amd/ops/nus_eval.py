@@ -64,10 +64,8 @@ def pred_to_global(boxes, scores, labels, counts, l2g, attr_moving, attr_still, 
     l2g = l2g.contiguous()
     mv = (ctypes.c_int32 * C)(*attr_moving)
     st = (ctypes.c_int32 * C)(*attr_still)
-    _lib.check(_lib.load().ud_nus_pred_to_global(
-        _lib.ptr(boxes), n, ncol, _lib.ptr(scores), _lib.ptr(labels), _lib.ptr(off_dev), max(B, 1), _lib.ptr(l2g), C,
-        ctypes.addressof(mv), ctypes.addressof(st), _lib.ptr(rec), _lib.ptr(cls), _lib.ptr(attr), _lib.ptr(status),
-        _lib.stream_of(rec)), "ud_nus_pred_to_global")
+    _lib.ud.ud_nus_pred_to_global(boxes, n, ncol, scores, labels, off_dev, max(B, 1), l2g, C, ctypes.addressof(mv),
+                                  ctypes.addressof(st), rec, cls, attr, status, _lib.stream_of(rec))
     return rec, cls, attr
 
 
@@ -86,6 +84,7 @@ def evaluate(cfg, pred, gt, S, P):
            "order": torch.empty((max(P, 1),), dtype=torch.int32, device=dev),
            "counts": torch.empty((2, C), dtype=torch.int32, device=dev),
            "status": torch.zeros((1,), dtype=torch.int32, device=dev)}
+    # struct fields, not call arguments: the addresses are stored as integers (pred, gt and out outlive the call)
     io = Io(pred_rec=_lib.ptr(pred["rec"]), pred_cls=_lib.ptr(pred["cls"]), pred_attr=_lib.ptr(pred["attr"]),
             pred_src=_lib.ptr(pred["src"]), pred_off=_lib.ptr(pred["off"]), gt_rec=_lib.ptr(gt["rec"]),
             gt_cls=_lib.ptr(gt["cls"]), gt_attr=_lib.ptr(gt["attr"]), gt_num_pts=_lib.ptr(gt["num_pts"]),
@@ -98,8 +97,7 @@ def evaluate(cfg, pred, gt, S, P):
     if nbytes == 0:
         raise ValueError(f"ud_nus_eval: {P} predictions / {C} classes are outside the supported sizes")
     ws = _lib.workspace(dev, nbytes, slot="nus_eval")
-    _lib.check(lib.ud_nus_eval(ctypes.addressof(cfg), ctypes.addressof(io), S, P, _lib.ptr(ws), ws.numel(),
-                               _lib.stream_of(ws)), "ud_nus_eval")
+    _lib.ud.ud_nus_eval(ctypes.addressof(cfg), ctypes.addressof(io), S, P, ws, ws.numel(), _lib.stream_of(ws))
     out["tp"] = out["tp"][:, :P]
     out["match_gt"] = out["match_gt"][:P]
     out["order"] = out["order"][:P]

@@ -247,29 +247,27 @@ class ClipAdamW(torch.optim.Optimizer):
                 self._state[ST_LR].fill_(lr)
                 self._lr_on_device = lr
             if self._n_chunks:
-                lib = _lib.load()
                 stream = _lib.stream_of(self._state)
                 pd = self._ptrs_dev
                 row = pd.stride(0) * 8
                 base = pd.data_ptr()
-                _lib.check(lib.ud_optim_sqnorm(self._chunks_dev.data_ptr(), self._n_chunks, base + 3 * row,
-                                               self._partial.data_ptr(), self._state.data_ptr(), stream),
-                           "ud_optim_sqnorm")
+                _lib.ud.ud_optim_sqnorm(self._chunks_dev.data_ptr(), self._n_chunks, base + 3 * row, self._partial.data_ptr(),
+                                        self._state.data_ptr(), stream)
                 max_norm = group.get("max_norm")
                 b1, b2 = group["betas"]
                 max_norm = float("inf") if max_norm is None else float(max_norm)
                 skip = 1 if group.get("skip_nonfinite", True) else 0
                 if self.ema_decay is None:
-                    _lib.check(lib.ud_optim_clip_adamw(
-                        self._chunks_dev.data_ptr(), self._n_chunks, base, base + row, base + 2 * row, base + 3 * row,
-                        self._partial.data_ptr(), self._state.data_ptr(), float(b1), float(b2), float(group["eps"]),
-                        float(group["weight_decay"]), max_norm, skip, stream), "ud_optim_clip_adamw")
+                    _lib.ud.ud_optim_clip_adamw(self._chunks_dev.data_ptr(), self._n_chunks, base, base + row, base + 2 * row,
+                                                base + 3 * row, self._partial.data_ptr(), self._state.data_ptr(), float(b1),
+                                                float(b2), float(group["eps"]), float(group["weight_decay"]), max_norm, skip,
+                                                stream)
                 else:
-                    _lib.check(lib.ud_optim_clip_adamw_ema(
-                        self._chunks_dev.data_ptr(), self._n_chunks, base, base + row, base + 2 * row, base + 4 * row,
-                        base + 3 * row, self._partial.data_ptr(), self._state.data_ptr(), float(b1), float(b2),
-                        float(group["eps"]), float(group["weight_decay"]), max_norm, skip, self.ema_decay,
-                        0.0 if self.ema_ramp is None else self.ema_ramp, stream), "ud_optim_clip_adamw_ema")
+                    _lib.ud.ud_optim_clip_adamw_ema(self._chunks_dev.data_ptr(), self._n_chunks, base, base + row,
+                                                    base + 2 * row, base + 4 * row, base + 3 * row, self._partial.data_ptr(),
+                                                    self._state.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                                                    float(group["weight_decay"]), max_norm, skip, self.ema_decay,
+                                                    0.0 if self.ema_ramp is None else self.ema_ramp, stream)
         return loss
 
     # ---- the weight average ---------------------------------------------------------------------------------------------
@@ -303,9 +301,8 @@ class ClipAdamW(torch.optim.Optimizer):
         with torch.cuda.device(self._dev):
             if self._n_chunks:
                 pd = self._ptrs_dev
-                _lib.check(_lib.load().ud_optim_swap(self._chunks_dev.data_ptr(), self._n_chunks, pd.data_ptr(),
-                                                     pd.data_ptr() + 4 * pd.stride(0) * 8, _lib.stream_of(self._state)),
-                           "ud_optim_swap")
+                _lib.ud.ud_optim_swap(self._chunks_dev.data_ptr(), self._n_chunks, pd.data_ptr(),
+                                      pd.data_ptr() + 4 * pd.stride(0) * 8, _lib.stream_of(self._state))
         self.ema_swapped = not self.ema_swapped
 
     @contextlib.contextmanager

@@ -60,9 +60,8 @@ class _SiteSet:
             if nbytes == 0:
                 raise ValueError(f"invalid sparse grid {self._grid()}")
             buf = torch.empty(nbytes, dtype=torch.uint8, device=self.indices.device)
-            _lib.check(lib.ud_spconv_build_index(_lib.ptr(self.indices), self.M, B, Dz, Hy, Wx,
-                                                 1 if self.rows_sorted else 0, _lib.ptr(buf), nbytes,
-                                                 _lib.stream_of(buf)), "ud_spconv_build_index")
+            _lib.ud.ud_spconv_build_index(self.indices, self.M, B, Dz, Hy, Wx, 1 if self.rows_sorted else 0, buf, nbytes,
+                                          _lib.stream_of(buf))
             self._index = buf
         return self._index
 
@@ -72,10 +71,8 @@ class _SiteSet:
             B, Dz, Hy, Wx = self._grid()
             K = ksize[0] * ksize[1] * ksize[2]
             rb = torch.empty((self.M, K), dtype=torch.int32, device=self.indices.device)
-            _lib.check(_lib.load().ud_spconv_subm_rulebook(
-                _lib.ptr(self.index()), 1 if self.rows_sorted else 0, _lib.ptr(self.indices), self.M,
-                B, Dz, Hy, Wx, ksize[0], ksize[1], ksize[2], _lib.ptr(rb), _lib.stream_of(rb)),
-                "ud_spconv_subm_rulebook")
+            _lib.ud.ud_spconv_subm_rulebook(self.index(), 1 if self.rows_sorted else 0, self.indices, self.M, B, Dz, Hy, Wx,
+                                            ksize[0], ksize[1], ksize[2], rb, _lib.stream_of(rb))
             self._subm[ksize] = rb
         return rb
 
@@ -101,21 +98,16 @@ class _SiteSet:
         out_coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
         m_out = torch.empty(1, dtype=torch.int32, device=dev)
         st = _lib.stream_of(out_coords)
-        _lib.check(lib.ud_spconv_down_outputs(_lib.ptr(self.indices), self.M, B, Dz, Hy, Wx,
-                                              _i3(ksize), _i3(stride), _i3(pad), _lib.ptr(out_index),
-                                              nbytes, _lib.ptr(out_coords), cap, _lib.ptr(m_out), st),
-                   "ud_spconv_down_outputs")
+        _lib.ud.ud_spconv_down_outputs(self.indices, self.M, B, Dz, Hy, Wx, _i3(ksize), _i3(stride), _i3(pad), out_index,
+                                       nbytes, out_coords, cap, m_out, st)
         Mout = int(m_out.item())                  # one host read per new level (sizes the tensors)
         out_coords = out_coords[:Mout]
         out_set = _SiteSet(out_coords, out_shape, B, rows_sorted=True)
         out_set._index = out_index
         out_nbr = torch.empty((Mout, K), dtype=torch.int32, device=dev)
         in_nbr = torch.empty((self.M, K), dtype=torch.int32, device=dev)
-        _lib.check(lib.ud_spconv_down_rulebook(_lib.ptr(self.index()), 1 if self.rows_sorted else 0,
-                                               self.M, B, Dz, Hy, Wx, _i3(ksize), _i3(stride),
-                                               _i3(pad), _lib.ptr(out_coords), Mout,
-                                               _lib.ptr(out_nbr), _lib.ptr(in_nbr), st),
-                   "ud_spconv_down_rulebook")
+        _lib.ud.ud_spconv_down_rulebook(self.index(), 1 if self.rows_sorted else 0, self.M, B, Dz, Hy, Wx, _i3(ksize),
+                                        _i3(stride), _i3(pad), out_coords, Mout, out_nbr, in_nbr, st)
         hit = (out_set, out_nbr, in_nbr)
         self._down[key] = hit
         return hit
@@ -138,8 +130,7 @@ class DeferredPyramid:
         B = self.B
         nbytes = lib.ud_spconv_index_bytes(B, *self.shape0, cap)
         self.index0 = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.ud_spconv_build_index_dev(_lib.ptr(coords_cap), _lib.ptr(m_dev), cap, B, *self.shape0, 0,
-                                                 _lib.ptr(self.index0), nbytes, st), "ud_spconv_build_index_dev")
+        _lib.ud.ud_spconv_build_index_dev(coords_cap, m_dev, cap, B, *self.shape0, 0, self.index0, nbytes, st)
         self.levels = []
         in_coords, in_cnt, in_cap, in_shape = coords_cap, m_dev, cap, self.shape0
         for ksize, stride, pad in geoms:
@@ -153,10 +144,8 @@ class DeferredPyramid:
             out_index = torch.empty(ob, dtype=torch.uint8, device=dev)
             out_coords = torch.empty((ocap, 4), dtype=torch.int32, device=dev)
             m_out = torch.empty(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.ud_spconv_down_outputs_dev(_lib.ptr(in_coords), _lib.ptr(in_cnt), in_cap, B, *in_shape,
-                                                      _i3(ksize), _i3(stride), _i3(pad), _lib.ptr(out_index), ob,
-                                                      _lib.ptr(out_coords), ocap, _lib.ptr(m_out), st),
-                       "ud_spconv_down_outputs_dev")
+            _lib.ud.ud_spconv_down_outputs_dev(in_coords, in_cnt, in_cap, B, *in_shape, _i3(ksize), _i3(stride), _i3(pad),
+                                               out_index, ob, out_coords, ocap, m_out, st)
             self.levels.append((out_shape, out_index, out_coords, m_out))
             in_coords, in_cnt, in_cap, in_shape = out_coords, m_out, ocap, out_shape
 
@@ -165,7 +154,6 @@ class DeferredPyramid:
 
     def finalize(self, M, level_counts):
         """M rows at level 0, level_counts[i] rows at strided level i (host ints) -> the level-0 _SiteSet, chain wired."""
-        lib = _lib.load()
         root = _SiteSet(self.coords_cap[:M], self.shape0, self.B, rows_sorted=False)
         root._index = self.index0
         cur = root
@@ -179,10 +167,8 @@ class DeferredPyramid:
             out_nbr = torch.empty((Mout, K), dtype=torch.int32, device=dev)
             in_nbr = torch.empty((cur.M, K), dtype=torch.int32, device=dev)
             B, Dz, Hy, Wx = cur._grid()
-            _lib.check(lib.ud_spconv_down_rulebook(_lib.ptr(cur.index()), 1 if cur.rows_sorted else 0, cur.M, B, Dz, Hy, Wx,
-                                                   _i3(ksize), _i3(stride), _i3(pad), _lib.ptr(oc), Mout,
-                                                   _lib.ptr(out_nbr), _lib.ptr(in_nbr), _lib.stream_of(oc)),
-                       "ud_spconv_down_rulebook")
+            _lib.ud.ud_spconv_down_rulebook(cur.index(), 1 if cur.rows_sorted else 0, cur.M, B, Dz, Hy, Wx, _i3(ksize),
+                                            _i3(stride), _i3(pad), oc, Mout, out_nbr, in_nbr, _lib.stream_of(oc))
             cur._down[(ksize, stride, pad)] = (out_set, out_nbr, in_nbr)
             cur = out_set
         return root
@@ -213,8 +199,7 @@ def mask_order(nbr, mirror=False):
             M = nbr.shape[0]
             ws = _lib.workspace(nbr.device, lib.ud_spconv_mask_order_workspace_bytes(M, K), "mask_order")
             order = torch.empty(M, dtype=torch.int32, device=nbr.device)
-            _lib.check(lib.ud_spconv_mask_order(_lib.ptr(nbr), M, K, _lib.ptr(order), _lib.ptr(ws), ws.numel(),
-                                                _lib.stream_of(nbr)), "ud_spconv_mask_order")
+            _lib.ud.ud_spconv_mask_order(nbr, M, K, order, ws, ws.numel(), _lib.stream_of(nbr))
         setattr(nbr, key, order)
     return None if order is False else order
 
@@ -231,12 +216,8 @@ def _conv(feat, nbr, weight, w_strides, mirror, bias, cin, cout, algo=0, scale=N
     order = mask_order(nbr, mirror) if algo in (0, 3) else None
     if feat.numel() * feat.element_size() >= 0xFFFF0000:
         raise ValueError("ud_spconv_conv: the input feature tensor must be smaller than 4 GiB - 64 KiB (32-bit byte offsets)")
-    _lib.check(_lib.load().ud_spconv_conv(_lib.ptr(feat), _lib.ptr(nbr), _lib.ptr(weight),
-                                          w_strides[0], w_strides[1], w_strides[2],
-                                          1 if mirror else 0, _lib.ptr(bias), _lib.ptr(out), Mout, K,
-                                          cin, cout, algo, _lib.ptr(order), _lib.ptr(scale),
-                                          _lib.ptr(shift), _lib.ptr(residual), 1 if relu else 0,
-                                          _lib.stream_of(feat)), "ud_spconv_conv")
+    _lib.ud.ud_spconv_conv(feat, nbr, weight, w_strides[0], w_strides[1], w_strides[2], 1 if mirror else 0, bias, out, Mout, K,
+                           cin, cout, algo, order, scale, shift, residual, 1 if relu else 0, _lib.stream_of(feat))
     return out
 
 
@@ -247,8 +228,7 @@ def tile_masks(nbr):
     if hit is None:
         Mout, K = nbr.shape
         hit = torch.empty(((Mout + 63) // 64,), dtype=torch.int32, device=nbr.device)
-        _lib.check(_lib.load().ud_spconv_tile_masks(_lib.ptr(nbr), Mout, K, _lib.ptr(mask_order(nbr, False)),
-                                                    _lib.ptr(hit), _lib.stream_of(nbr)), "ud_spconv_tile_masks")
+        _lib.ud.ud_spconv_tile_masks(nbr, Mout, K, mask_order(nbr, False), hit, _lib.stream_of(nbr))
         nbr._ud_tile_masks = hit
     return hit
 
@@ -281,13 +261,8 @@ def _conv_bf16io(feat, nbr, weight, bias, cin, cout, scale=None, shift=None, res
         residual = residual.to(torch.bfloat16)
     out = torch.empty((Mout, cout), dtype=torch.bfloat16, device=feat.device)
     order = mask_order(nbr, mirror)
-    _lib.check(_lib.load().ud_spconv_conv_bf16io(_lib.ptr(feat), _lib.ptr(nbr), _lib.ptr(weight),
-                                                 K * cin, cin, 1, 1 if mirror else 0, _lib.ptr(bias),
-                                                 _lib.ptr(out),
-                                                 Mout, K, cin, cout, io, _lib.ptr(order),
-                                                 _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
-                                                 1 if relu else 0, _lib.stream_of(feat)),
-               "ud_spconv_conv_bf16io")
+    _lib.ud.ud_spconv_conv_bf16io(feat, nbr, weight, K * cin, cin, 1, 1 if mirror else 0, bias, out, Mout, K, cin, cout, io,
+                                  order, scale, shift, residual, 1 if relu else 0, _lib.stream_of(feat))
     return out
 
 
@@ -410,10 +385,8 @@ class _SparseConvFn(torch.autograd.Function):
                 else:
                     # narrow layers (register-staged kernel): it follows row_order for both operands itself
                     g_rows, io, row_order, nbr_rows = gout, 1, order, nbr
-                _lib.check(lib.ud_spconv_wgrad_bf16(_lib.ptr(features), _lib.ptr(nbr_rows),
-                                                    _lib.ptr(g_rows), _lib.ptr(gw), Mout, K, cin, cout, io,
-                                                    _lib.ptr(row_order), _lib.ptr(tile_masks(nbr)), _lib.ptr(ws),
-                                                    ws.numel(), _lib.stream_of(w)), "ud_spconv_wgrad_bf16")
+                _lib.ud.ud_spconv_wgrad_bf16(features, nbr_rows, g_rows, gw, Mout, K, cin, cout, io, row_order, tile_masks(nbr),
+                                             ws, ws.numel(), _lib.stream_of(w))
             if has_bias and ctx.needs_input_grad[2]:
                 gb = bn_act.bias_grad(gout)
             return gin, gw, gb, None, None, None, None
@@ -426,17 +399,12 @@ class _SparseConvFn(torch.autograd.Function):
             if algo == 3 and K <= 32:       # bf16 operands staged from fp32 tensors
                 need = lib.ud_spconv_wgrad_bf16_workspace_bytes(Mout, K, cin, cout)
                 ws = _lib.workspace(w.device, need, "spconv_wgrad")
-                _lib.check(lib.ud_spconv_wgrad_bf16(_lib.ptr(features), _lib.ptr(nbr), _lib.ptr(gout),
-                                                    _lib.ptr(gw), Mout, K, cin, cout, 0,
-                                                    _lib.ptr(mask_order(nbr, False)),
-                                                    _lib.ptr(tile_masks(nbr)), _lib.ptr(ws),
-                                                    ws.numel(), _lib.stream_of(w)), "ud_spconv_wgrad_bf16")
+                _lib.ud.ud_spconv_wgrad_bf16(features, nbr, gout, gw, Mout, K, cin, cout, 0, mask_order(nbr, False),
+                                             tile_masks(nbr), ws, ws.numel(), _lib.stream_of(w))
             else:
                 need = lib.ud_spconv_wgrad_workspace_bytes(Mout, K, cin, cout)
                 ws = _lib.workspace(w.device, need, "spconv_wgrad")
-                _lib.check(lib.ud_spconv_wgrad(_lib.ptr(features), _lib.ptr(nbr), _lib.ptr(gout),
-                                               _lib.ptr(gw), Mout, K, cin, cout, algo, _lib.ptr(ws),
-                                               ws.numel(), _lib.stream_of(w)), "ud_spconv_wgrad")
+                _lib.ud.ud_spconv_wgrad(features, nbr, gout, gw, Mout, K, cin, cout, algo, ws, ws.numel(), _lib.stream_of(w))
         if has_bias and ctx.needs_input_grad[2]:
             gb = bn_act.bias_grad(gout)
         return gin, gw, gb, None, None, None, None
@@ -451,9 +419,7 @@ class _DenseFn(torch.autograd.Function):
         dense = torch.empty((B, C, Dz, Hy, Wx), dtype=torch.float32, device=features.device)
         lib = _lib.load()
         ws = _lib.workspace(features.device, lib.ud_sparse_bev_workspace_bytes(B, Dz, Hy, Wx), "sparse_bev")
-        _lib.check(lib.ud_sparse_to_dense(_lib.ptr(features), _lib.ptr(indices), M, C, B, Dz, Hy, Wx,
-                                          _lib.ptr(dense), _lib.ptr(ws), ws.numel(), _lib.stream_of(dense)),
-                   "ud_sparse_to_dense")
+        _lib.ud.ud_sparse_to_dense(features, indices, M, C, B, Dz, Hy, Wx, dense, ws, ws.numel(), _lib.stream_of(dense))
         ctx.save_for_backward(indices)
         ctx.grid = grid
         ctx.mc = (M, C)
@@ -468,9 +434,7 @@ class _DenseFn(torch.autograd.Function):
         g = torch.zeros((M, C), dtype=torch.float32, device=gdense.device)    # rows outside the grid: 0
         lib = _lib.load()
         ws = _lib.workspace(g.device, lib.ud_sparse_bev_workspace_bytes(B, Dz, Hy, Wx), "sparse_bev")
-        _lib.check(lib.ud_dense_to_sparse(_lib.ptr(gdense), _lib.ptr(indices), M, C, B, Dz, Hy, Wx,
-                                          _lib.ptr(g), _lib.ptr(ws), ws.numel(), _lib.stream_of(g)),
-                   "ud_dense_to_sparse")
+        _lib.ud.ud_dense_to_sparse(gdense, indices, M, C, B, Dz, Hy, Wx, g, ws, ws.numel(), _lib.stream_of(g))
         return g, None, None
 
 
@@ -490,9 +454,8 @@ class _BevFn(torch.autograd.Function):
         f32 = features.dtype == torch.float32
         bev = torch.empty((B, Hy, Wx, C * Dz), dtype=features.dtype, device=features.device)
         ws = _lib.workspace(features.device, lib.ud_sparse_bev_workspace_bytes(B, Dz, Hy, Wx), "sparse_bev")
-        fn = lib.ud_sparse_to_bev_f32 if f32 else lib.ud_sparse_to_bev_bf16
-        _lib.check(fn(_lib.ptr(features), _lib.ptr(indices), M, C, B, Dz, Hy, Wx, _lib.ptr(bev), _lib.ptr(ws), ws.numel(),
-                      _lib.stream_of(bev)), "ud_sparse_to_bev")
+        fn = _lib.ud.ud_sparse_to_bev_f32 if f32 else _lib.ud.ud_sparse_to_bev_bf16
+        fn(features, indices, M, C, B, Dz, Hy, Wx, bev, ws, ws.numel(), _lib.stream_of(bev))
         ctx.save_for_backward(indices)
         ctx.cfg = (grid, M, C, features.dtype)
         return bev.permute(0, 3, 1, 2)
@@ -505,9 +468,8 @@ class _BevFn(torch.autograd.Function):
         g = gbev.to(dt).permute(0, 2, 3, 1).contiguous()
         gfeat = torch.zeros((M, C), dtype=dt, device=g.device)
         ws = _lib.workspace(g.device, lib.ud_sparse_bev_workspace_bytes(B, Dz, Hy, Wx), "sparse_bev")
-        fn = lib.ud_bev_to_sparse_f32 if dt == torch.float32 else lib.ud_bev_to_sparse_bf16
-        _lib.check(fn(_lib.ptr(g), _lib.ptr(indices), M, C, B, Dz, Hy, Wx, _lib.ptr(gfeat), _lib.ptr(ws), ws.numel(),
-                      _lib.stream_of(g)), "ud_bev_to_sparse")
+        fn = _lib.ud.ud_bev_to_sparse_f32 if dt == torch.float32 else _lib.ud.ud_bev_to_sparse_bf16
+        fn(g, indices, M, C, B, Dz, Hy, Wx, gfeat, ws, ws.numel(), _lib.stream_of(g))
         return gfeat, None, None
 
 

@@ -27,8 +27,7 @@ def _packed(conv):
         host = w.detach().to("cpu", torch.float32)
         out = torch.empty(7 * 6 * 4 * 16 * 4, dtype=torch.float32)
         sn, sc, sky, skx = host.stride()
-        _lib.check(_lib.load().ud_stem_pack_weights(host.data_ptr(), sn, sc, sky, skx, out.data_ptr()),
-                   "ud_stem_pack_weights")
+        _lib.ud.ud_stem_pack_weights(host.data_ptr(), sn, sc, sky, skx, out.data_ptr())
         hit = (key, out.to(w.device))
         conv._ud_stem_pack = hit
     return hit[1]
@@ -39,7 +38,6 @@ def stem(x, conv, bn, out_dtype=torch.float32, pool=True):
     _lib.require_gpu(x)
     if not supported(x, conv, bn):
         raise ValueError("stem(): frozen 7x7 / stride-2 stem with eval-mode BatchNorm on a float32 GPU image batch expected")
-    lib = _lib.load()
     B, _, H, W = x.shape
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     dev = x.device
@@ -50,13 +48,11 @@ def stem(x, conv, bn, out_dtype=torch.float32, pool=True):
     y = torch.empty((B, OH, OW, 64), dtype=out_dtype, device=dev)
     sb, sc, sy, sx = x.stride()
     st = _lib.stream_of(x)
-    _lib.check(lib.ud_stem_conv7x7_bn_relu(x.data_ptr(), sb, sc, sy, sx, B, H, W, wpk.data_ptr(), vec[3].data_ptr(),
-                                           vec[4].data_ptr(), y.data_ptr(), 1 if bf16 else 0, st),
-               "ud_stem_conv7x7_bn_relu")
+    _lib.ud.ud_stem_conv7x7_bn_relu(x.data_ptr(), sb, sc, sy, sx, B, H, W, wpk.data_ptr(), vec[3].data_ptr(), vec[4].data_ptr(),
+                                    y.data_ptr(), 1 if bf16 else 0, st)
     if not pool:
         return y.permute(0, 3, 1, 2)
     PH, PW = (OH - 1) // 2 + 1, (OW - 1) // 2 + 1
     z = torch.empty((B, PH, PW, 64), dtype=out_dtype, device=dev)
-    _lib.check(lib.ud_maxpool3x3s2_nhwc(y.data_ptr(), z.data_ptr(), B, OH, OW, 64, 1 if bf16 else 0, st),
-               "ud_maxpool3x3s2_nhwc")
+    _lib.ud.ud_maxpool3x3s2_nhwc(y.data_ptr(), z.data_ptr(), B, OH, OW, 64, 1 if bf16 else 0, st)
     return z.permute(0, 3, 1, 2)                  # logical NCHW, channels-last memory

@@ -82,10 +82,8 @@ def voxelize_batch(points, voxel_size, pc_range, max_points, max_voxels, want_vo
                                                                       ((1,) if B * N < SMALL_CLOUD else (0, 1)))
     for a in order:
         _forget(ws)                                          # unknown until the call has returned
-        _lib.check(lib.ud_voxelize(_lib.ptr(points), B, N, F, _f3(voxel_size), _f3(pc_range),
-                                   int(max_points), int(max_voxels), _lib.ptr(voxels), _lib.ptr(coords),
-                                   _lib.ptr(num), _lib.ptr(mean), _lib.ptr(m_out), _lib.ptr(ws),
-                                   ws.numel(), a, _lib.stream_of(points)), "ud_voxelize")
+        _lib.ud.ud_voxelize(points, B, N, F, _f3(voxel_size), _f3(pc_range), int(max_points), int(max_voxels), voxels, coords,
+                            num, mean, m_out, ws, ws.numel(), a, _lib.stream_of(points))
         m_host = m_out.cpu()
         if int(m_host[B + 1]) == 0:
             _note_algo(ws, a, B, N, int(max_points), int(max_voxels))
@@ -129,9 +127,8 @@ def voxelize_deferred(points, voxel_size, pc_range, max_points, max_voxels, want
             raise ValueError("ud_voxelize: algo 2 takes at most 256 tiles of 1 024 points, P <= 16, B <= 64")
         algo = small
     _forget(ws)
-    _lib.check(lib.ud_voxelize(_lib.ptr(points), B, N, F, _f3(voxel_size), _f3(pc_range), int(max_points),
-                               int(max_voxels), _lib.ptr(voxels), _lib.ptr(coords), _lib.ptr(num), _lib.ptr(mean),
-                               _lib.ptr(m_out), _lib.ptr(ws), ws.numel(), algo, _lib.stream_of(points)), "ud_voxelize")
+    _lib.ud.ud_voxelize(points, B, N, F, _f3(voxel_size), _f3(pc_range), int(max_points), int(max_voxels), voxels, coords, num,
+                        mean, m_out, ws, ws.numel(), algo, _lib.stream_of(points))
     # the caller reads m_out[B + 1] and answers with voxelize_confirm (== 0) or voxelize_dirty (refused / overflowed: the workspace is
     # dirty); until then the note is pending and the next small call runs algo 2 (memset first)
     _note_algo(ws, algo, B, N, int(max_points), int(max_voxels), pending=True)

@@ -2,14 +2,11 @@
 the recurrence, skipped steps and gradient-less tensors included; the EMA arguments are validated; the new entry points are
 declared, exported and reject bad arguments without a GPU."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from ema_reference import ClipAdamWEmaReference, EmaReference
 
 EMA_SYMBOLS = ("ud_optim_clip_adamw_ema", "ud_optim_swap")
@@ -139,13 +136,10 @@ def test_reference_gradient_less_tensor_converges_to_its_value():
 
 def test_ema_symbols_declared_and_exported(hip_lib):
     from unidistill_amd import _lib
-    text = open(os.path.join(ROOT, "include", "unidistill_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(ud_[a-z0-9_]+)\s*\(", text))
+    declared = _lib.exported_symbols()      # the prototypes parsed from unidistill_hip.h (test_abi.py counts them independently)
     for n in EMA_SYMBOLS:
         assert n in declared, f"{n} not declared in unidistill_hip.h"
         assert hasattr(hip_lib, n), f"{n} declared in unidistill_hip.h but not exported"
-        assert n in _lib.exported_symbols()
 
 
 def test_ema_launchers_reject_bad_arguments_without_a_gpu(hip_lib):

@@ -16,7 +16,6 @@ w = torch.randn(N, K, device=d) * 0.05
 y = torch.empty(P, N, device=d)
 ws = torch.empty(lib.ud_conv1x1p_f32_workspace_bytes(), dtype=torch.uint8, device=d)
 for _ in range(13):
-    _lib.check(lib.ud_conv1x1p_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), P, K, N, None, None, None, None, 0, None, 0, None,
-                                        None, None, 0, 0, _lib.ptr(ws) if use_ws else None, ws.numel() if use_ws else 0,
-                                        _lib.stream_of(x)), "ud_conv1x1p_nhwc_f32")
+    _lib.ud.ud_conv1x1p_nhwc_f32(x, w, y, P, K, N, None, None, None, None, 0, None, 0, None, None, None, 0, 0,
+                                 ws if use_ws else None, ws.numel() if use_ws else 0, _lib.stream_of(x))
 torch.cuda.synchronize()

@@ -36,17 +36,14 @@ def timeit(f, n=20):
 
 def new(x, w, y, P, K, N, bias=None, scale=None, shift=None, res=None, relu=0, part=None, use_ws=True):
     sl = ct.c_int(0)
-    _lib.check(lib.ud_conv1x1p_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), P, K, N, _lib.ptr(bias), _lib.ptr(scale),
-                                        _lib.ptr(shift), _lib.ptr(res), relu, _lib.ptr(part),
-                                        part.numel() * 4 if part is not None else 0, ct.byref(sl), None, None, 0, 0,
-                                        _lib.ptr(ws) if use_ws else None, ws.numel() if use_ws else 0, _lib.stream_of(x)),
-               "ud_conv1x1p_nhwc_f32")
+    _lib.ud.ud_conv1x1p_nhwc_f32(x, w, y, P, K, N, bias, scale, shift, res, relu, part,
+                                 part.numel() * 4 if part is not None else 0, ct.byref(sl), None, None, 0, 0,
+                                 ws if use_ws else None, ws.numel() if use_ws else 0, _lib.stream_of(x))
     return sl.value
 
 
 def old(x, w, y, P, K, N):
-    _lib.check(lib.ud_conv1x1_nhwc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), P, K, N, None, None, None, None, 0, _lib.stream_of(x)),
-               "ud_conv1x1_nhwc_f32")
+    _lib.ud.ud_conv1x1_nhwc_f32(x, w, y, P, K, N, None, None, None, None, 0, _lib.stream_of(x))
 
 
 tot_o = tot_n = 0.0

@@ -25,8 +25,7 @@ def bench(B, sweeps, fused):
     if ALGO >= 2 and (B * N + 1023) // 1024 > 256:
         return
     def run(algo=ALGO):
-        _lib.check(lib.ud_voxelize(_lib.ptr(pts), B, N, F, vs, rg, P, maxM, _lib.ptr(vox), _lib.ptr(coords),
-                                   _lib.ptr(num), _lib.ptr(mean), _lib.ptr(m), _lib.ptr(ws), ws.numel(), algo, st), "vox")
+        _lib.ud.ud_voxelize(pts, B, N, F, vs, rg, P, maxM, vox, coords, num, mean, m, ws, ws.numel(), algo, st)
     if ALGO == 3: run(2)      # leaves the workspace clean
     for _ in range(3): run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
