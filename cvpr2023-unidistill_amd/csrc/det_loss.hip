@@ -277,6 +277,10 @@ __global__ __launch_bounds__(256) void k_reg_fwd(RegArgs a, const long long* __r
 }
 
 // dhead[t][b][j][pix] = g_box[t][j] * L_box[j] + g_iou[t] * L_iou[j] (+ g_aw[t] * L_aw for the iou head)
+// Precondition: the positive (mask != 0) slots of one (task, sample) name pairwise distinct pixels.  The store below does not
+// accumulate, so of two positive slots on one pixel only one gradient would survive (which one is a race).  The assigner
+// guarantees it (FCOSAssigner._assign_windowed / _assign_dense, csrc/assign.hip: one positive slot per anchor point);
+// tests/test_det_loss_reference_cpu.py and tests/test_det_loss_reference_gpu.py assert it on the crowded trials.
 template <bool ROT>
 __global__ __launch_bounds__(256) void k_reg_bwd(RegArgs a, const long long* __restrict__ ind,
                                                  const unsigned char* __restrict__ mask,

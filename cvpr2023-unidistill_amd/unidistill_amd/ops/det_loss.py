@@ -139,7 +139,10 @@ def reg_terms(preds, ind, mask, tgt, num_obj, sx, sy, nb=10, iou_mode="reference
     """preds: per-task dicts of head tensors; ind/mask [T,B,K], tgt [T,B,K,>=nb], num_obj [T]
     -> (box_loss [T,10], iou_loss [T], iou_aware [T]) normalised like the reference.
     iou_mode "reference": the reference's axis-aligned IoU loss and nearest-BEV IoU-aware target; "rotated3d": both from the
-    rotated 3-D IoU of the decoded prediction and target (box_loss is the same either way).  Gradients go to the heads only."""
+    rotated 3-D IoU of the decoded prediction and target (box_loss is the same either way).  Gradients go to the heads only.
+    Precondition: the positive (mask) slots of one (task, sample) name pairwise distinct pixels in ``ind``.  The backward stores a slot's
+    gradient at its pixel and does not accumulate, so a second positive slot on the same pixel would silently lose one of the two.  The
+    assigner's output satisfies it (one positive slot per anchor point; tests/test_dense_head.py, tests/test_det_loss_reference_gpu.py)."""
     heads = [pd[name] for pd in preds for name in HEADS]
     fn = _RegFn
     if check_iou_mode(iou_mode) == "rotated3d":

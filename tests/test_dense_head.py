@@ -135,6 +135,7 @@ def test_windowed_assignment_equals_dense_formulation():
     """The 9x9-window target assignment == the all-anchors formulation, incl. boxes at / beyond the
     range border, many boxes per task and empty tasks (bit-exact integer targets, equal encodings)."""
     import torch
+    from det_loss_cases import positive_pixels_distinct
     head = _head()
     asg = head.target_assigner
     g = torch.Generator().manual_seed(11)
@@ -162,3 +163,8 @@ def test_windowed_assignment_equals_dense_formulation():
         for key in ("heatmap", "ind", "mask", "cat", "box_encoding"):
             for t in a[key]:
                 assert torch.equal(a[key][t], b_[key][t]), (trial, key, t)
+        # what the detection loss's regression backward takes for granted (it stores, it does not accumulate): the positive slots of
+        # one (task, sample) name pairwise distinct pixels -- also where many boxes share their nearest anchors (trial 3)
+        for form in (a, b_):
+            for t in form["ind"]:
+                assert positive_pixels_distinct(form["ind"][t], form["mask"][t]), (trial, t)

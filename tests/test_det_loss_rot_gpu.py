@@ -9,14 +9,13 @@ import math
 import pytest
 import torch
 
+import det_loss_cases as C
 import rot_iou_reference as R
 
 pytestmark = pytest.mark.gpu
 
 T, B, K, H, W = 2, 2, 16, 8, 8
 SX, SY = 0.6, 0.8
-WIDTH = (2, 1, 3, 2, 2, 1)          # reg height dim rot vel iou
-NAMES = ("reg", "height", "dim", "rot", "vel", "iou")
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,62 +50,11 @@ def _case(nb, scenario):
 
 
 def _preds(planes, packed):
-    """Head tensors [B, c, H, W] per task from planes [T,B,11,HW]: separate contiguous leaves, or channel slices of ONE packed leaf with
-    a spare channel between the heads (what PackedSepHeads returns).  -> (preds, leaves)."""
-    preds, leaves = [], []
-    if packed:
-        pk = torch.zeros(B, T * 11 + T * 6, H, W, device="cuda")
-        c = 0
-        slots = []
-        for t in range(T):
-            j = 0
-            for wd in WIDTH:
-                pk[:, c:c + wd] = planes[t, :, j:j + wd].reshape(B, wd, H, W).cuda()
-                slots.append((c, wd))
-                c += wd + 1
-                j += wd
-        pk.requires_grad_(True)
-        leaves.append(pk)
-        it = iter(slots)
-        for t in range(T):
-            preds.append({nm: pk[:, c0:c0 + wd] for nm, (c0, wd) in zip(NAMES, (next(it) for _ in NAMES))})
-        return preds, leaves, slots
-    for t in range(T):
-        pd, j = {}, 0
-        for nm, wd in zip(NAMES, WIDTH):
-            pd[nm] = planes[t, :, j:j + wd].reshape(B, wd, H, W).cuda().contiguous().requires_grad_(True)
-            leaves.append(pd[nm])
-            j += wd
-        preds.append(pd)
-    return preds, leaves, None
+    return C.preds_from_planes(planes, packed, H, W)
 
 
 def _plane_grads(leaves, slots, packed):
-    """-> [T,B,11,HW] gradient planes on the CPU (zeros where a head got none)."""
-    out = torch.zeros(T, B, 11, H * W)
-    if packed:
-        gr = leaves[0].grad.cpu()
-        it = iter(slots)
-        for t in range(T):
-            j = 0
-            for wd in WIDTH:
-                c0, _ = next(it)
-                out[t, :, j:j + wd] = gr[:, c0:c0 + wd].reshape(B, wd, H * W)
-                j += wd
-        used = torch.zeros(gr.shape[1], dtype=torch.bool)
-        for c0, wd in slots:
-            used[c0:c0 + wd] = True
-        assert float(gr[:, ~used].abs().max()) == 0.0          # the spare channels between the heads stay untouched
-        return out
-    it = iter(leaves)
-    for t in range(T):
-        j = 0
-        for wd in WIDTH:
-            leaf = next(it)
-            if leaf.grad is not None:
-                out[t, :, j:j + wd] = leaf.grad.cpu().reshape(B, wd, H * W)
-            j += wd
-    return out
+    return C.plane_grads(leaves, slots, packed, T, B, H * W)
 
 
 def _bits(x):
