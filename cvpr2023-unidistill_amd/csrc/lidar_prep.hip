@@ -14,6 +14,16 @@
 //   k_lidar_scatter  recomputes the test and writes each kept row at its rank (tile offset + earlier waves + mbcnt);
 //                    the blocks past the tiles write the zero padding rows count_b .. Nmax.
 // The host reads the counts back between the scan and the scatter to size Nmax.
+//
+// GT-sampling paste (ud_lidar_paste_count / ud_lidar_paste_compact) runs the same three kernels with a
+// per-segment record (UdLidarPasteSeg) and per-sample removal boxes; the kernels are templates on that, so the plain
+// entry points compile to the code they had.  A segment may read its rows from another buffer (the object database),
+// is dropped whole when its gate byte is 0, and is an object or a scene segment.  A scene row is dropped when its
+// float32 position after the segment transform, before BDA, lies inside a removal box whose accept byte is set:
+//   sx = x - cx, sy = y - cy;  |z - cz| <= dz / 2;
+//   lx = sx * cos(yaw) + sy * sin(yaw),  ly = -sx * sin(yaw) + sy * cos(yaw);  |lx| < dx / 2 + 1e-5, |ly| < dy / 2 + 1e-5
+// in float32 (OpenPCDet's check_pt_in_box3d).  Every workgroup stages its sample's accepted boxes once in LDS as
+// centre, half extents (+1e-5 on x / y) and sin / cos.
 #include "ud_common.h"
 #include "ud_prof.h"
 #include "points_xform.h"
@@ -28,6 +38,54 @@ constexpr int kMaxSeg = UD_LIDAR_MAX_SEGMENTS;
 // seg_par[s]: see UD_LIDAR_SEG_PAR in unidistill_hip.h; smp_par[b]: UD_LIDAR_SMP_PAR.
 constexpr int kSegMat = 0, kSegLast = 16, kSegXform = 17;
 constexpr int kSmpBda = 0, kSmpRange = 16, kSmpHasBda = 22, kSmpHasRange = 23;
+
+// An accepted removal box as the inside test reads it.
+struct RmBox {
+  float cx, cy, cz, hx, hy, hz, sn, cs;
+};
+
+// The paste arguments of a launch (all NULL / 0 for a segment table alone).
+struct PasteArgs {
+  const UdLidarPasteSeg* seg;      // [S] or NULL
+  const float* rm_boxes;           // [R][7]
+  const int64_t* rm_off;           // [B + 1] or NULL: no removal boxes
+  const uint8_t* rm_accept;        // box j of sample b: rm_accept[b * rm_stride + j]
+  int64_t rm_stride;
+};
+
+// Stages sample b's accepted removal boxes in LDS, in order (wave 0; ends with a barrier).  -> their number.
+__device__ __forceinline__ int stage_rm_boxes(const PasteArgs& pa, int b, RmBox* s_rm, int* s_nrm) {
+  if (threadIdx.x < 64) {
+    int n = 0;
+    int64_t r0 = 0;
+    if (pa.rm_off) {
+      r0 = pa.rm_off[b];
+      const int64_t n64 = pa.rm_off[b + 1] - r0;
+      n = n64 < 0 ? 0 : (n64 > UD_GT_PASTE_MAX_CAND ? UD_GT_PASTE_MAX_CAND : (int)n64);          // host-checked
+    }
+    const int j = threadIdx.x;
+    const bool on = j < n && pa.rm_accept[(int64_t)b * pa.rm_stride + j] != 0;
+    const unsigned long long m = __ballot(on);
+    if (on) {
+      const float* q = pa.rm_boxes + (r0 + j) * 7;
+      RmBox r;
+      r.cx = q[0], r.cy = q[1], r.cz = q[2];
+      r.hx = q[3] / 2 + 1e-5f, r.hy = q[4] / 2 + 1e-5f, r.hz = q[5] / 2;
+      r.sn = sinf(q[6]), r.cs = cosf(q[6]);
+      s_rm[__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = r;
+    }
+    if (j == 0) *s_nrm = __popcll(m);
+  }
+  __syncthreads();
+  return *s_nrm;
+}
+
+__device__ __forceinline__ bool in_rm_box(const RmBox& r, const float xyz[3]) {
+  const float sx = xyz[0] - r.cx, sy = xyz[1] - r.cy;
+  if (!(fabsf(xyz[2] - r.cz) <= r.hz)) return false;
+  const float lx = sx * r.cs + sy * r.sn, ly = -sx * r.sn + sy * r.cs;
+  return fabsf(lx) < r.hx && fabsf(ly) < r.hy;
+}
 
 struct SampleRows {
   int64_t row0, rows;
@@ -50,13 +108,24 @@ __device__ __forceinline__ SampleRows load_sample(const int64_t* __restrict__ se
 
 // One input row through the chain: xyz after the sweep transform (a key-frame row is copied) and BDA, each rounded to
 // float32; returns the range test.  sp / bp: the row's segment and sample parameters.
+// With kPaste the row is dropped between the two transforms when its segment's gate is closed or, for a scene
+// segment, when it lies inside one of the n_rm staged removal boxes.
+template <bool kPaste>
 __device__ __forceinline__ bool lidar_row(const float* __restrict__ p, const double* __restrict__ sp,
-                                          const double* __restrict__ bp, float xyz[3]) {
+                                          const double* __restrict__ bp, float xyz[3],
+                                          const UdLidarPasteSeg* ps = nullptr, const RmBox* s_rm = nullptr,
+                                          int n_rm = 0) {
   xyz[0] = p[0], xyz[1] = p[1], xyz[2] = p[2];
   if (sp[kSegXform] != 0.0) {
     float t[3];
     ud_points_xform(sp + kSegMat, xyz[0], xyz[1], xyz[2], t);
     xyz[0] = t[0], xyz[1] = t[1], xyz[2] = t[2];
+  }
+  if (kPaste) {
+    if (ps && ps->gate && *ps->gate == 0) return false;
+    if (!ps || !ps->object)
+      for (int j = 0; j < n_rm; ++j)
+        if (in_rm_box(s_rm[j], xyz)) return false;
   }
   if (bp[kSmpHasBda] != 0.0) {
     float t[3];
@@ -74,25 +143,37 @@ __device__ __forceinline__ int find_segment(const int64_t* s_off, int nseg, int6
   return k;
 }
 
+// The row's source: the shared cloud, or the segment's own buffer (rows counted from the segment's first).
+__device__ __forceinline__ const float* row_source(const float* __restrict__ pts, int D, const UdLidarPasteSeg* ps,
+                                                   int64_t row, int64_t seg_row0) {
+  return ps && ps->src ? ps->src + (row - seg_row0) * D : pts + row * D;
+}
+
+template <bool kPaste>
 __global__ __launch_bounds__(kTile) void k_lidar_count(const float* __restrict__ pts, int D,
                                                        const int64_t* __restrict__ seg,
                                                        const int64_t* __restrict__ sseg,
                                                        const double* __restrict__ seg_par,
                                                        const double* __restrict__ smp_par,
-                                                       int* __restrict__ tile_cnt, int64_t T) {
+                                                       int* __restrict__ tile_cnt, int64_t T, PasteArgs pa) {
   __shared__ int64_t s_off[kMaxSeg + 1];
   __shared__ int s_wave[kWaves];
+  __shared__ RmBox s_rm[kPaste ? 64 : 1];
+  __shared__ int s_nrm;
   const int b = blockIdx.y;
   const int64_t t = blockIdx.x;
   const SampleRows sr = load_sample(seg, sseg, b, s_off);
+  const int n_rm = kPaste ? stage_rm_boxes(pa, b, s_rm, &s_nrm) : 0;
   const int64_t i = t * kTile + threadIdx.x;
   bool keep = false;
   if (i < sr.rows) {
     const int64_t row = sr.row0 + i;
     const int k = find_segment(s_off, sr.nseg, row);
+    const UdLidarPasteSeg* ps = kPaste && pa.seg ? pa.seg + sr.seg0 + k : nullptr;
     float xyz[3];
-    keep = lidar_row(pts + row * D, seg_par + (sr.seg0 + k) * UD_LIDAR_SEG_PAR, smp_par + (int64_t)b * UD_LIDAR_SMP_PAR,
-                     xyz);
+    keep = lidar_row<kPaste>(kPaste ? row_source(pts, D, ps, row, s_off[k]) : pts + row * D,
+                             seg_par + (sr.seg0 + k) * UD_LIDAR_SEG_PAR, smp_par + (int64_t)b * UD_LIDAR_SMP_PAR, xyz,
+                             ps, s_rm, n_rm);
   }
   const unsigned long long m = __ballot(keep);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
@@ -133,6 +214,7 @@ __global__ __launch_bounds__(kTile) void k_lidar_scan(const int* __restrict__ ti
 
 // blockIdx.x < T: tile t of sample b's input rows; blockIdx.x >= T: zero padding of sample b (padded output only).
 // compact == 0: out [B][nmax][D], sample b at row b * nmax; compact == 1: samples back to back, no padding.
+template <bool kPaste>
 __global__ __launch_bounds__(kTile) void k_lidar_scatter(const float* __restrict__ pts, int D,
                                                          const int64_t* __restrict__ seg,
                                                          const int64_t* __restrict__ sseg,
@@ -140,10 +222,13 @@ __global__ __launch_bounds__(kTile) void k_lidar_scatter(const float* __restrict
                                                          const double* __restrict__ smp_par,
                                                          const int64_t* __restrict__ tile_off,
                                                          const int64_t* __restrict__ counts, int64_t T, int64_t nmax,
-                                                         int compact, float* __restrict__ out, int64_t out_rows) {
+                                                         int compact, float* __restrict__ out, int64_t out_rows,
+                                                         PasteArgs pa) {
   __shared__ int64_t s_off[kMaxSeg + 1];
   __shared__ int64_t s_red[kTile];
   __shared__ int s_wave[kWaves];
+  __shared__ RmBox s_rm[kPaste ? 64 : 1];
+  __shared__ int s_nrm;
   const int b = blockIdx.y;
   const int64_t t = blockIdx.x;
   if (t >= T) {                                                      // block-uniform: no barrier below
@@ -159,6 +244,7 @@ __global__ __launch_bounds__(kTile) void k_lidar_scatter(const float* __restrict
     return;
   }
   const SampleRows sr = load_sample(seg, sseg, b, s_off);
+  const int n_rm = kPaste ? stage_rm_boxes(pa, b, s_rm, &s_nrm) : 0;
   int64_t base = (int64_t)b * nmax;
   if (compact) {                                                     // rows kept by the samples before b
     int64_t s = 0;
@@ -176,11 +262,14 @@ __global__ __launch_bounds__(kTile) void k_lidar_scatter(const float* __restrict
   float xyz[3] = {0.0f, 0.0f, 0.0f};
   int64_t row = 0;
   const double* sp = seg_par;
+  const float* src = pts;
   if (i < sr.rows) {
     row = sr.row0 + i;
     const int k = find_segment(s_off, sr.nseg, row);
     sp = seg_par + (sr.seg0 + k) * UD_LIDAR_SEG_PAR;
-    keep = lidar_row(pts + row * D, sp, smp_par + (int64_t)b * UD_LIDAR_SMP_PAR, xyz);
+    const UdLidarPasteSeg* ps = kPaste && pa.seg ? pa.seg + sr.seg0 + k : nullptr;
+    src = kPaste ? row_source(pts, D, ps, row, s_off[k]) : pts + row * D;
+    keep = lidar_row<kPaste>(src, sp, smp_par + (int64_t)b * UD_LIDAR_SMP_PAR, xyz, ps, s_rm, n_rm);
   }
   const unsigned long long m = __ballot(keep);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -192,7 +281,6 @@ __global__ __launch_bounds__(kTile) void k_lidar_scatter(const float* __restrict
   rank += __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
   const int64_t o = base + rank;
   if (o >= out_rows) return;                                         // cannot happen for a consistent plan
-  const float* src = pts + row * D;
   float* dst = out + o * D;
   dst[0] = xyz[0];
   dst[1] = xyz[1];
@@ -238,22 +326,30 @@ int check_dev(const int64_t* seg_dev, const int64_t* sseg_dev, const double* seg
   return UD_OK;
 }
 
-}  // namespace
 
-extern "C" size_t ud_lidar_prep_workspace_bytes(const int64_t* seg_host, const int64_t* sample_seg_host, int S,
-                                                int B) {
-  if (check_plan(nullptr, seg_host && S >= 0 ? seg_host[S] : 0, 3, seg_host, sample_seg_host, S, B, false) != UD_OK)
-    return 0;
-  return ws_bytes_for(B, tiles_of(seg_host, sample_seg_host, B));
+// Host validation of the paste arguments.  pa.seg may be NULL (no gates, no foreign sources, every segment a scene
+// segment) and pa.rm_off NULL (no removal boxes).
+int check_paste(const PasteArgs& pa, const int64_t* rm_off_host, int B) {
+  if ((pa.rm_off == nullptr) != (rm_off_host == nullptr)) return UD_ERR_INVALID_ARG;
+  if (!rm_off_host) return UD_OK;
+  if (rm_off_host[0] < 0 || pa.rm_stride < 0) return UD_ERR_INVALID_ARG;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = rm_off_host[b + 1] - rm_off_host[b];
+    if (n < 0 || n > UD_GT_PASTE_MAX_CAND || n > pa.rm_stride) return UD_ERR_INVALID_ARG;
+  }
+  if (B > 0 && rm_off_host[B] > rm_off_host[0] && (!pa.rm_boxes || !pa.rm_accept)) return UD_ERR_INVALID_ARG;
+  return UD_OK;
 }
 
-extern "C" int ud_lidar_prep_count(const float* pts, int64_t rows, int D, const int64_t* seg_host,
-                                   const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
-                                   const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
-                                   int64_t* counts, void* workspace, size_t workspace_bytes, ud_stream_t stream_) {
-  int rc = check_plan(pts, rows, D, seg_host, sample_seg_host, S, B);
+// The two entry points' work; pa == nullptr: the plain chain.
+int run_count(const float* pts, int64_t rows, int D, const int64_t* seg_host, const int64_t* sample_seg_host, int S, int B,
+              const int64_t* seg_dev, const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+              int64_t* counts, void* workspace, size_t workspace_bytes, hipStream_t stream, const PasteArgs* pa,
+              const int64_t* rm_off_host) {
+  int rc = check_plan(pts, rows, D, seg_host, sample_seg_host, S, B, !(pa && pa->seg));
   if (rc != UD_OK) return rc;
   if ((rc = check_dev(seg_dev, sample_seg_dev, seg_par, smp_par, S, B)) != UD_OK) return rc;
+  if (pa && (rc = check_paste(*pa, rm_off_host, B)) != UD_OK) return rc;
   if (B == 0) return UD_OK;
   if (!counts) return UD_ERR_INVALID_ARG;
   const int64_t T = tiles_of(seg_host, sample_seg_host, B);
@@ -262,11 +358,14 @@ extern "C" int ud_lidar_prep_count(const float* pts, int64_t rows, int D, const 
   if (need > 0 && (!workspace || workspace_bytes < need)) return UD_ERR_WORKSPACE;
   int* tile_cnt = (int*)workspace;
   int64_t* tile_off = (int64_t*)((char*)workspace + align16((size_t)(B * T) * 4));
-  hipStream_t stream = (hipStream_t)stream_;
   if (T > 0) {
-    UdProfScope prof("input.k_lidar_count", stream);
-    k_lidar_count<<<dim3((unsigned)T, B), kTile, 0, stream>>>(pts, D, seg_dev, sample_seg_dev, seg_par, smp_par,
-                                                               tile_cnt, T);
+    UdProfScope prof(pa ? "input.k_lidar_count_paste" : "input.k_lidar_count", stream);
+    if (pa)
+      k_lidar_count<true><<<dim3((unsigned)T, B), kTile, 0, stream>>>(pts, D, seg_dev, sample_seg_dev, seg_par, smp_par,
+                                                                        tile_cnt, T, *pa);
+    else
+      k_lidar_count<false><<<dim3((unsigned)T, B), kTile, 0, stream>>>(pts, D, seg_dev, sample_seg_dev, seg_par,
+                                                                         smp_par, tile_cnt, T, PasteArgs{});
     UD_LAUNCH_CHECK();
   }
   UdProfScope prof("input.k_lidar_scan", stream);
@@ -275,15 +374,15 @@ extern "C" int ud_lidar_prep_count(const float* pts, int64_t rows, int D, const 
   return UD_OK;
 }
 
-extern "C" int ud_lidar_prep_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host,
-                                     const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
-                                     const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
-                                     const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact,
-                                     float* out, int64_t out_rows, void* workspace, size_t workspace_bytes,
-                                     ud_stream_t stream_) {
-  int rc = check_plan(pts, rows, D, seg_host, sample_seg_host, S, B);
+int run_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host, const int64_t* sample_seg_host, int S,
+                int B, const int64_t* seg_dev, const int64_t* sample_seg_dev, const double* seg_par,
+                const double* smp_par, const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact,
+                float* out, int64_t out_rows, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                const PasteArgs* pa, const int64_t* rm_off_host) {
+  int rc = check_plan(pts, rows, D, seg_host, sample_seg_host, S, B, !(pa && pa->seg));
   if (rc != UD_OK) return rc;
   if ((rc = check_dev(seg_dev, sample_seg_dev, seg_par, smp_par, S, B)) != UD_OK) return rc;
+  if (pa && (rc = check_paste(*pa, rm_off_host, B)) != UD_OK) return rc;
   if (B == 0) return UD_OK;
   if (!counts_host || !counts || nmax < 0 || out_rows < 0 || (out_rows > 0 && !out)) return UD_ERR_INVALID_ARG;
   int64_t total = 0, lo = nmax;
@@ -302,11 +401,67 @@ extern "C" int ud_lidar_prep_compact(const float* pts, int64_t rows, int D, cons
   if (T + P == 0) return UD_OK;
   if (T + P > 0x7fffffffLL) return UD_ERR_INVALID_ARG;
   const int64_t* tile_off = (const int64_t*)((const char*)workspace + align16((size_t)(B * T) * 4));
-  hipStream_t stream = (hipStream_t)stream_;
-  UdProfScope prof("input.k_lidar_scatter", stream);
-  k_lidar_scatter<<<dim3((unsigned)(T + P), B), kTile, 0, stream>>>(pts, D, seg_dev, sample_seg_dev, seg_par, smp_par,
-                                                                     tile_off, counts, T, nmax, compact ? 1 : 0, out,
-                                                                     out_rows);
+  UdProfScope prof(pa ? "input.k_lidar_scatter_paste" : "input.k_lidar_scatter", stream);
+  if (pa)
+    k_lidar_scatter<true><<<dim3((unsigned)(T + P), B), kTile, 0, stream>>>(
+        pts, D, seg_dev, sample_seg_dev, seg_par, smp_par, tile_off, counts, T, nmax, compact ? 1 : 0, out, out_rows, *pa);
+  else
+    k_lidar_scatter<false><<<dim3((unsigned)(T + P), B), kTile, 0, stream>>>(
+        pts, D, seg_dev, sample_seg_dev, seg_par, smp_par, tile_off, counts, T, nmax, compact ? 1 : 0, out, out_rows,
+        PasteArgs{});
   UD_LAUNCH_CHECK();
   return UD_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ud_lidar_prep_workspace_bytes(const int64_t* seg_host, const int64_t* sample_seg_host, int S,
+                                                int B) {
+  if (check_plan(nullptr, seg_host && S >= 0 ? seg_host[S] : 0, 3, seg_host, sample_seg_host, S, B, false) != UD_OK)
+    return 0;
+  return ws_bytes_for(B, tiles_of(seg_host, sample_seg_host, B));
+}
+
+extern "C" int ud_lidar_prep_count(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                                   const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                                   const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                                   int64_t* counts, void* workspace, size_t workspace_bytes, ud_stream_t stream_) {
+  return run_count(pts, rows, D, seg_host, sample_seg_host, S, B, seg_dev, sample_seg_dev, seg_par, smp_par, counts,
+                   workspace, workspace_bytes, (hipStream_t)stream_, nullptr, nullptr);
+}
+
+extern "C" int ud_lidar_prep_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                                     const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                                     const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                                     const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact,
+                                     float* out, int64_t out_rows, void* workspace, size_t workspace_bytes,
+                                     ud_stream_t stream_) {
+  return run_compact(pts, rows, D, seg_host, sample_seg_host, S, B, seg_dev, sample_seg_dev, seg_par, smp_par,
+                     counts_host, counts, nmax, compact, out, out_rows, workspace, workspace_bytes, (hipStream_t)stream_,
+                     nullptr, nullptr);
+}
+
+extern "C" int ud_lidar_paste_count(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                                    const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                                    const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                                    const UdLidarPasteSeg* seg_paste, const float* rm_boxes, const int64_t* rm_off_host,
+                                    const int64_t* rm_off_dev, const uint8_t* rm_accept, int64_t rm_stride,
+                                    int64_t* counts, void* workspace, size_t workspace_bytes, ud_stream_t stream_) {
+  const PasteArgs pa{seg_paste, rm_boxes, rm_off_dev, rm_accept, rm_stride};
+  return run_count(pts, rows, D, seg_host, sample_seg_host, S, B, seg_dev, sample_seg_dev, seg_par, smp_par, counts,
+                   workspace, workspace_bytes, (hipStream_t)stream_, &pa, rm_off_host);
+}
+
+extern "C" int ud_lidar_paste_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                                      const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                                      const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                                      const UdLidarPasteSeg* seg_paste, const float* rm_boxes,
+                                      const int64_t* rm_off_host, const int64_t* rm_off_dev, const uint8_t* rm_accept,
+                                      int64_t rm_stride, const int64_t* counts_host, const int64_t* counts, int64_t nmax,
+                                      int compact, float* out, int64_t out_rows, void* workspace, size_t workspace_bytes,
+                                      ud_stream_t stream_) {
+  const PasteArgs pa{seg_paste, rm_boxes, rm_off_dev, rm_accept, rm_stride};
+  return run_compact(pts, rows, D, seg_host, sample_seg_host, S, B, seg_dev, sample_seg_dev, seg_par, smp_par,
+                     counts_host, counts, nmax, compact, out, out_rows, workspace, workspace_bytes, (hipStream_t)stream_,
+                     &pa, rm_off_host);
 }

@@ -1,0 +1,482 @@
+"""GT-sampling (database paste) for the device LiDAR input chain.
+
+The reference's GTSampling (transforms3d.py:162-207 -> OpenPCDet's DataBaseSampler) sits between CollectLidarSweeps and
+BevAffineTransformation.  Split as the other LiDAR transforms are: in the loader ``GTSampling`` only draws candidate
+indices (host, a handful of integers) and records them in data_dict["lidar_aug"]["paste"]; after collate one tiny launch
+(ud_gt_paste_select) decides which candidates collide with nothing, and the fused chain (ud_lidar_paste_count /
+ud_lidar_paste_compact) reads the accepted objects' clouds straight out of the device-resident ``ObjectDatabase``,
+drops the scene's points inside their boxes and goes on with BDA, range filter, compaction and padding as before.
+Images are not edited (the reference's MultiModalGTSampling is a no-op too): a camera branch sees the unpasted scene.
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+
+MAX_CAND = 63            # include/unidistill_hip.h UD_GT_PASTE_MAX_CAND
+
+
+def _input_prep():
+    from . import input_prep          # imported late: input_prep re-exports this module's names
+    return input_prep
+
+
+def _parse_cfg(entries):
+    """["car:5", ...] -> [("car", 5), ...]"""
+    out = []
+    for e in entries or []:
+        name, num = str(e).split(":")
+        out.append((name, int(num)))
+    return out
+
+
+class ObjectDatabase:
+    """The ground-truth database of OpenPCDet's create_groundtruth_database, resident on the device: every object's
+    box-centred cloud back to back in ``points`` f32 [P, D], ``offsets`` int64 [N + 1] (object i = rows offsets[i] ..
+    offsets[i+1]), ``boxes`` f32 [N, W >= 7] with every column kept (velocity included) and ``class_ids`` int64 [N]
+    into ``class_names``.  boxes / offsets / class_ids are held on the host as well (numpy: the sampler and the collate
+    read a few dozen of them per sample) and on the device (``boxes_d``, ``offsets_d``, ``class_ids_d``).  Pickling a
+    database (a loader worker returning a paste record) sends its name only; the receiving process must hold a database
+    of that name."""
+
+    _registry = {}
+
+    def __init__(self, points, offsets, boxes, class_ids, class_names, device="cuda", name=None):
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, np.float32))
+        if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] < 3:
+            raise ValueError("points must be float32 [P, D >= 3]")
+        self.offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        self.boxes = np.ascontiguousarray(boxes, np.float32)
+        self.class_ids = np.ascontiguousarray(class_ids, np.int64).reshape(-1)
+        self.class_names = [str(c) for c in class_names]
+        n = len(self.class_ids)
+        if self.boxes.ndim != 2 or self.boxes.shape[1] < 7 or self.boxes.shape[0] != n or len(self.offsets) != n + 1:
+            raise ValueError("boxes must be [N, >= 7], class_ids [N], offsets [N + 1]")
+        if self.offsets[0] != 0 or self.offsets[-1] != pts.shape[0] or (np.diff(self.offsets) < 0).any():
+            raise ValueError("offsets must ascend from 0 to the number of points")
+        if n and (self.class_ids.min() < 0 or self.class_ids.max() >= len(self.class_names)):
+            raise ValueError("class_ids must index class_names")
+        device = torch.device(device)
+        self.points = pts.to(device).contiguous()
+        self.boxes_d = torch.from_numpy(self.boxes).to(device)
+        self.offsets_d = torch.from_numpy(self.offsets).to(device)
+        self.class_ids_d = torch.from_numpy(self.class_ids).to(device)
+        self.name = name if name is not None else f"db{len(ObjectDatabase._registry)}"
+        ObjectDatabase._registry[self.name] = self
+
+    @staticmethod
+    def lookup(name):
+        return ObjectDatabase._registry[name]
+
+    def __reduce__(self):
+        return ObjectDatabase.lookup, (self.name,)
+
+    def __len__(self):
+        return len(self.class_ids)
+
+    @property
+    def D(self):
+        return int(self.points.shape[1])
+
+    @property
+    def rows(self):
+        return np.diff(self.offsets)
+
+    def indices_of(self, class_name):
+        """Database indices of one class, ascending."""
+        if class_name not in self.class_names:
+            return np.zeros(0, np.int64)
+        return np.nonzero(self.class_ids == self.class_names.index(class_name))[0]
+
+    @classmethod
+    def from_arrays(cls, points, offsets, boxes, class_ids, class_names, device="cuda", filter_by_min_points_cfg=None,
+                    num_points=None, name=None):
+        """``filter_by_min_points_cfg`` (["car:5", ...], OpenPCDet's filter_by_min_points) drops, at construction, the
+        objects of a named class with fewer points than its threshold; ``num_points`` is the dbinfos' num_points_in_gt
+        (default: the stored rows)."""
+        pts = points.cpu().numpy() if torch.is_tensor(points) else np.asarray(points, np.float32)
+        offsets = np.asarray(offsets, np.int64).reshape(-1)
+        boxes, class_ids = np.asarray(boxes, np.float32), np.asarray(class_ids, np.int64).reshape(-1)
+        class_names = [str(c) for c in class_names]
+        rows = np.diff(offsets)
+        npts = rows if num_points is None else np.asarray(num_points, np.int64).reshape(-1)
+        keep = np.ones(len(class_ids), bool)
+        for cname, least in _parse_cfg(filter_by_min_points_cfg):
+            if cname in class_names:
+                keep &= ~((class_ids == class_names.index(cname)) & (npts < least))
+        if not keep.all():
+            sel = np.nonzero(keep)[0]
+            pts = np.concatenate([pts[offsets[i]:offsets[i + 1]] for i in sel]) if len(sel) else pts[:0]
+            offsets = np.concatenate([[0], np.cumsum(rows[sel])]).astype(np.int64)
+            boxes, class_ids = boxes[sel], class_ids[sel]
+        return cls(np.ascontiguousarray(pts, np.float32), offsets, boxes, class_ids, class_names, device, name)
+
+    @classmethod
+    def from_infos(cls, db_infos, load_points, class_names=None, device="cuda", filter_by_min_points_cfg=None,
+                   name=None):
+        """OpenPCDet's dbinfos layout {class: [{"box3d_lidar", "num_points_in_gt", "path", ...}]}; ``load_points(info)``
+        returns the object's box-centred float32 [n, D] cloud (e.g. np.fromfile(root / info["path"]).reshape(-1, D))."""
+        class_names = list(db_infos.keys()) if class_names is None else [str(c) for c in class_names]
+        clouds, boxes, ids, npts = [], [], [], []
+        for k, cname in enumerate(class_names):
+            for info in db_infos.get(cname, []):
+                clouds.append(np.asarray(load_points(info), np.float32))
+                boxes.append(np.asarray(info["box3d_lidar"], np.float32))
+                ids.append(k)
+                npts.append(int(info.get("num_points_in_gt", len(clouds[-1]))))
+        if not clouds:
+            raise ValueError("db_infos holds no object of class_names")
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])])
+        return cls.from_arrays(np.concatenate(clouds), offsets, np.stack(boxes), ids, class_names, device,
+                               filter_by_min_points_cfg, npts, name)
+
+
+class GTSampling:
+    """GTSampling (transforms3d.py:162-207) split for the device: ``set_epoch`` / ``forward`` / ``stop_epoch`` as the
+    reference (the identity from epoch + 1 >= stop_epoch on, and when ``points`` is absent).  In the loader it does the
+    host part of DataBaseSampler only: per ``sampler_groups`` entry ("class:N") it draws N candidates -- max(0, N minus
+    the class's boxes in the scene) with ``limit_whole_scene`` -- from a per-class shuffled index list with a moving
+    pointer, reshuffled when exhausted (sample_with_fixed_number), with its own numpy Generator.  It records in
+    data_dict["lidar_aug"]["paste"] the candidates' database indices, groups and labels, a copy of the pre-BDA gt_boxes,
+    remove_extra_width and the database; ``points`` and ``gt_boxes`` are not changed.  Collision selection, point
+    removal, paste and the appended boxes happen after collate (collate_fn / lidar_prep_host_clouds).  Must run before
+    BevAffineTransformation and ObjectRangeFilter."""
+
+    def __init__(self, database, class_names, sampler_groups, remove_extra_width=(0, 0, 0), limit_whole_scene=False,
+                 stop_epoch=None, seed=None, use_road_plane=False):
+        if use_road_plane:
+            raise NotImplementedError("GTSampling: use_road_plane is not supported")
+        self.database = database
+        self.class_names = [str(c) for c in class_names]
+        self.groups = [(g, name, num) for g, (name, num) in enumerate(_parse_cfg(sampler_groups))
+                       if name in self.class_names]
+        if sum(num for _, _, num in self.groups) > MAX_CAND:
+            raise ValueError(f"sampler_groups ask for {sum(num for _, _, num in self.groups)} candidates per scene, "
+                             f"the device selection takes at most {MAX_CAND}")
+        self.remove_extra_width = tuple(float(v) for v in remove_extra_width)
+        if len(self.remove_extra_width) != 3:
+            raise ValueError("remove_extra_width needs three values")
+        self.limit_whole_scene = bool(limit_whole_scene)
+        self.stop_epoch = stop_epoch
+        self.epoch = -1
+        self.rng = np.random.default_rng(seed)
+        # sample_with_fixed_number's state per class: the pointer starts past the end, so the first draw shuffles
+        self.state = {}
+        for _, name, _ in self.groups:
+            ids = database.indices_of(name)
+            self.state[name] = {"ids": ids, "pointer": len(ids), "indices": np.arange(len(ids))}
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+
+    def sample_with_fixed_number(self, class_name, num):
+        """OpenPCDet's draw: a slice of the class's shuffled list at the pointer (short at the end of the list), the
+        list reshuffled first when the pointer has reached its end.  -> database indices."""
+        st = self.state[class_name]
+        if st["pointer"] >= len(st["ids"]):
+            st["indices"] = self.rng.permutation(len(st["ids"]))
+            st["pointer"] = 0
+        take = st["indices"][st["pointer"]:st["pointer"] + num]
+        st["pointer"] += num
+        return st["ids"][take]
+
+    def _scene_counts(self, data_dict):
+        names = data_dict.get("gt_names", None)
+        if names is not None:
+            names = np.asarray(names)
+            return {n: int((names == n).sum()) for _, n, _ in self.groups}
+        labels = data_dict.get("gt_labels", None)
+        if labels is None:
+            return {n: 0 for _, n, _ in self.groups}
+        labels = np.asarray(labels)
+        return {n: int((labels == self.class_names.index(n)).sum()) for _, n, _ in self.groups}
+
+    def forward(self, data_dict):
+        if self.stop_epoch is not None and (self.epoch + 1) >= self.stop_epoch:
+            return data_dict
+        if data_dict.get("points", None) is None:
+            return data_dict
+        a = _input_prep()._lidar_aug(data_dict)
+        if a.get("bda_mat") is not None or a.get("range") is not None:
+            raise ValueError("GTSampling must come before BevAffineTransformation and ObjectRangeFilter")
+        counts = self._scene_counts(data_dict) if self.limit_whole_scene else None
+        idx, grp = [], []
+        for g, name, num in self.groups:
+            n = max(0, num - counts[name]) if counts is not None else num
+            if n <= 0 or len(self.state[name]["ids"]) == 0:
+                continue
+            got = self.sample_with_fixed_number(name, n)
+            idx.append(got)
+            grp.append(np.full(len(got), g, np.int32))
+        idx = np.concatenate(idx).astype(np.int64) if idx else np.zeros(0, np.int64)
+        grp = np.concatenate(grp) if grp else np.zeros(0, np.int32)
+        db_names = np.asarray(self.database.class_names, object)[self.database.class_ids[idx]]
+        a["paste"] = {"database": self.database, "cand_idx": idx, "cand_group": grp,
+                      "cand_labels": np.array([self.class_names.index(n) for n in db_names], np.int64),
+                      "gt_boxes": np.array(data_dict.get("gt_boxes", np.zeros((0, 7), np.float32)), np.float32,
+                                           copy=True),
+                      "remove_extra_width": self.remove_extra_width}
+        return data_dict
+
+    def __call__(self, data_dict):
+        return self.forward(data_dict)
+
+
+def check_segments(sweeps, candidates, sample=None):
+    """The chain takes UD_LIDAR_MAX_SEGMENTS = 64 segments per sample: key frame + sweeps + candidates."""
+    ip = _input_prep()
+    where = "" if sample is None else f"sample {sample}: "
+    if candidates > MAX_CAND:
+        raise ValueError(f"{where}{candidates} candidates, the device selection takes at most {MAX_CAND}")
+    if 1 + sweeps + candidates > ip._MAX_SEG:
+        raise ValueError(f"{where}1 key frame + {sweeps} sweeps + {candidates} candidates = "
+                         f"{1 + sweeps + candidates} segments, the chain takes at most {ip._MAX_SEG}")
+
+
+def _pack(arrays):
+    """[(name, array)] -> (uint8 buffer with 16-byte aligned sections, {name: (offset, array)})."""
+    ip = _input_prep()
+    parts, off = {}, 0
+    for name, a in arrays:
+        parts[name] = (off, a)
+        off = ip._align16(off + a.nbytes)
+    buf = np.zeros(max(off, 16), np.uint8)
+    for o, a in parts.values():
+        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    return buf, parts
+
+
+def _paste_plan(scenes, pastes, D):
+    """Host plan of a paste batch.  scenes: per sample (rows per scene segment, matrices, transform flags, last-column
+    values, BDA, range) as _plan_segments gives them; pastes: per sample the paste record or None.  Object segments go
+    ahead of the sample's scene segments.  -> (arrays in plan order with the pointers still relative, ncmax, scene rows); the
+    ``pseg`` rows are (src, gate, object): src of an object segment is absolute (the database), src of a scene segment
+    is the byte offset of its first row inside the scene buffer, gate the byte offset inside the accept block."""
+    ip = _input_prep()
+    B = len(scenes)
+    ncs = [0 if p is None else len(p["cand_idx"]) for p in pastes]
+    for b, ((rows, *_), nc) in enumerate(zip(scenes, ncs)):
+        check_segments(len(rows) - 1, nc, b)
+    ncmax = max(ncs) if ncs else 0
+    seg_rows, nseg, mats, xform, last, bdas, ranges, pseg = [], [], [], [], [], [], [], []
+    gts, cands, rms, groups = [], [], [], []
+    scene_row = 0
+    for b, ((rows, m, x, l, bda, rg), p) in enumerate(zip(scenes, pastes)):
+        if p is not None and ncs[b]:
+            db = p["database"]
+            if db.D != D:
+                raise ValueError(f"the database's clouds have {db.D} columns, the scene's {D}")
+            _lib.require_gpu(db.points)
+            idx = np.asarray(p["cand_idx"], np.int64)
+            boxes = db.boxes[idx, :7]
+            for c, i in enumerate(idx):
+                t = np.eye(4)
+                t[:3, 3] = boxes[c, :3]                         # database clouds are box-centred
+                mats.append(t)
+                pseg.append((db.points.data_ptr() + int(db.offsets[i]) * D * 4, 1 + b * ncmax + c, 1))
+            seg_rows += [int(v) for v in db.rows[idx]]
+            xform += [True] * ncs[b]
+            last += [np.nan] * ncs[b]                           # the time-lag column is kept as stored
+            rm = boxes.copy()
+            rm[:, 3:6] += np.asarray(p["remove_extra_width"], np.float32)
+            cands.append(boxes)
+            rms.append(rm)
+            groups.append(np.asarray(p["cand_group"], np.int32))
+        g = np.zeros((0, 7), np.float32) if p is None else np.asarray(p["gt_boxes"], np.float32)
+        gts.append(g[:, :7] if g.ndim == 2 and len(g) else np.zeros((0, 7), np.float32))
+        for r in rows:
+            pseg.append((scene_row * D * 4, 0, 0))
+            scene_row += int(r)
+        seg_rows += [int(r) for r in rows]
+        nseg.append(ncs[b] + len(rows))
+        mats += list(m)
+        xform += list(x)
+        last += list(l)
+        bdas.append(bda)
+        ranges.append(rg)
+    _, base = ip._lidar_tables(seg_rows, nseg, mats, xform, last, bdas, ranges)
+    cat = lambda xs, w, dt: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros((0,) + w, dt), dt)
+    off = lambda ns: np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    arrays = [(k, base[k][1]) for k in ("seg", "sseg", "seg_par", "smp_par")]
+    arrays += [("pseg", np.array(pseg, np.int64).reshape(-1, 3)), ("gt", cat(gts, (7,), np.float32)),
+               ("gt_off", off([len(g) for g in gts])), ("cand", cat(cands, (7,), np.float32)),
+               ("cand_off", off(ncs)), ("cand_group", cat(groups, (), np.int32)), ("rm", cat(rms, (7,), np.float32))]
+    return arrays, ncmax, scene_row
+
+
+def _resolve(arrays, scene_ptr, accept_ptr):
+    """Turns the relative pointers of ``pseg`` into addresses (gate 0 = no gate; stored offsets are 1-based)."""
+    out = []
+    for name, a in arrays:
+        if name == "pseg":
+            a = a.copy()
+            scene = a[:, 2] == 0
+            a[scene, 0] += scene_ptr
+            a[~scene, 1] += accept_ptr - 1
+        out.append((name, a))
+    return out
+
+
+def _paste_run(D, parts, plan_base, B, ncmax, result_d, device, stream, out_compact):
+    """ud_gt_paste_select -> ud_lidar_paste_count -> ONE readback of [counts | accept bytes] (waits on ``stream``
+    only) -> ud_lidar_paste_compact, all on ``stream`` (current while this runs).
+    -> (out, counts int64 numpy [B], accept uint8 numpy [B, ncmax])."""
+    lib = _lib.load()
+    seg, sseg = parts["seg"][1], parts["sseg"][1]
+    gt_off, cand_off = parts["gt_off"][1], parts["cand_off"][1]
+    S = len(seg) - 1
+    rows = int(seg[-1])
+    p = {k: plan_base + o for k, (o, _) in parts.items()}
+    ws_bytes = int(lib.ud_lidar_prep_workspace_bytes(seg.ctypes.data, sseg.ctypes.data, S, B))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    hs = stream.cuda_stream
+    counts_ptr, accept_ptr = result_d.data_ptr(), result_d.data_ptr() + 8 * B
+    _lib.ud.ud_gt_paste_select(p["gt"], gt_off.ctypes.data, p["gt_off"], p["cand"], p["cand_group"],
+                               cand_off.ctypes.data, p["cand_off"], B, accept_ptr, ncmax, hs)
+    args = (None, rows, D, seg.ctypes.data, sseg.ctypes.data, S, B, p["seg"], p["sseg"], p["seg_par"], p["smp_par"],
+            p["pseg"], p["rm"], cand_off.ctypes.data, p["cand_off"], accept_ptr, ncmax)
+    _lib.ud.ud_lidar_paste_count(*args, counts_ptr, ws, ws_bytes, hs)
+    result_h = torch.empty(result_d.numel(), dtype=torch.uint8, pin_memory=True)
+    result_h.copy_(result_d, non_blocking=True)         # counts and accept bytes: one copy, one event
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    ev.synchronize()
+    rh = result_h.numpy()
+    counts = rh[:8 * B].view(np.int64).copy()
+    accept = rh[8 * B:8 * B + B * ncmax].reshape(B, ncmax).copy()
+    nmax = int(counts.max()) if B else 0
+    if out_compact:
+        out = torch.empty((int(counts.sum()), D), dtype=torch.float32, device=device)
+    else:
+        out = torch.empty((B, nmax, D), dtype=torch.float32, device=device)
+    _lib.ud.ud_lidar_paste_compact(*args, counts.ctypes.data, counts_ptr, nmax, 1 if out_compact else 0, out,
+                                   out.numel() // D, ws, ws_bytes, hs)
+    return out, counts, accept
+
+
+def _store_accept(pastes, accept):
+    for b, p in enumerate(pastes):
+        if p is not None:
+            p["accept"] = accept[b, :len(p["cand_idx"])].astype(bool)
+
+
+def lidar_paste_host_clouds(clouds, plans, device, compact=False):
+    """lidar_prep_host_clouds for a batch in which at least one sample's lidar_aug record carries a ``paste`` record
+    (GTSampling): selection, then the fused chain with point removal and the accepted objects' clouds ahead of each
+    sample's scene (concatenate([obj_points, points])), BDA / range filter / padding as without paste.  One H2D copy
+    (scene clouds + plan), four launches, one host wait.  Each paste record gets ``accept`` (bool per candidate).
+    -> (points f32 [B, Nmax, D], or [sum(counts), D] with ``compact``; counts int64 [B]; accept uint8 [B, Ncmax])."""
+    ip = _input_prep()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+    arrs, D = ip._host_clouds(clouds, plans)
+    pastes = [None if a is None else a.get("paste") for a in plans]
+    scenes = []
+    for cs, aug in zip(arrs, plans):
+        m, x, l, bda, rg = ip._plan_segments(cs, aug, D)
+        scenes.append(([len(a) for a in cs], m, x, l, bda, rg))
+    arrays, ncmax, rows = _paste_plan(scenes, pastes, D)
+    B = len(arrs)
+    plan_bytes = len(_pack(arrays)[0])
+    pts_bytes = ip._align16(rows * D * 4)
+    i = ip._device_index(device)
+    device = torch.device("cuda", i)
+    host, copied = ip._staging(i, pts_bytes + plan_bytes)
+    hv = host.numpy()
+    fv = hv[:rows * D * 4].view(np.float32)
+    off = 0
+    for cs in arrs:
+        for a in cs:
+            fv[off:off + a.size] = a.reshape(-1)
+            off += a.size
+    cur = torch.cuda.current_stream(device)
+    s = ip.input_stream(device)
+    with torch.cuda.stream(s):
+        dev = torch.empty(pts_bytes + plan_bytes, dtype=torch.uint8, device=device)
+        result_d = torch.empty(8 * B + B * ncmax, dtype=torch.uint8, device=device)
+        plan, parts = _pack(_resolve(arrays, dev.data_ptr(), result_d.data_ptr() + 8 * B))
+        hv[pts_bytes:pts_bytes + plan_bytes] = plan
+        dev.copy_(host[:dev.numel()], non_blocking=True)
+        copied.record(s)
+        out, counts, accept = _paste_run(D, parts, dev.data_ptr() + pts_bytes, B, ncmax, result_d, device, s, compact)
+        done = torch.cuda.Event()
+        done.record(s)
+    cur.wait_event(done)
+    out.record_stream(cur)
+    _store_accept(pastes, accept)
+    return out, counts, accept
+
+
+def gt_paste(points, seg, gt_boxes, database, cand_idx, cand_group, remove_extra_width=(0, 0, 0)):
+    """The paste alone on device clouds: ``points`` f32 [rows, D], the samples' scenes back to back, ``seg`` their row
+    offsets (B + 1 ints); per sample ``gt_boxes`` [M_b, >= 7], ``cand_idx`` database indices and ``cand_group`` their
+    ascending group ids (a single array each for B == 1).  Candidates are selected by the DataBaseSampler rule, scene
+    points inside an accepted candidate's box (enlarged by ``remove_extra_width``) are dropped, the accepted objects'
+    clouds are placed ahead of their sample's scene.  No sweep transform, BDA or range filter.  Runs on the current
+    stream; one host wait.  -> (points_out f32 [sum(counts), D], counts int64 numpy [B], accept uint8 numpy [B, Ncmax])."""
+    _lib.require_gpu(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous():
+        raise ValueError("points must be a contiguous float32 [rows, D >= 3] tensor")
+    rows, D = points.shape
+    seg = [int(v) for v in seg]
+    if len(seg) < 2 or seg[0] != 0 or seg[-1] != rows or any(b < a for a, b in zip(seg, seg[1:])):
+        raise ValueError("seg must ascend from 0 to the number of rows")
+    B = len(seg) - 1
+    if B == 1 and not isinstance(cand_idx, (list, tuple)):
+        gt_boxes, cand_idx, cand_group = [gt_boxes], [cand_idx], [cand_group]
+    if not (len(gt_boxes) == len(cand_idx) == len(cand_group) == B):
+        raise ValueError("one gt_boxes / cand_idx / cand_group entry per sample")
+    rew = tuple(float(v) for v in remove_extra_width)
+    pastes, scenes = [], []
+    for b in range(B):
+        idx, grp = np.asarray(cand_idx[b], np.int64).reshape(-1), np.asarray(cand_group[b], np.int32).reshape(-1)
+        if len(idx) != len(grp):
+            raise ValueError(f"sample {b}: {len(idx)} candidates, {len(grp)} groups")
+        pastes.append({"database": database, "cand_idx": idx, "cand_group": grp,
+                       "gt_boxes": np.asarray(gt_boxes[b], np.float32),
+                       "remove_extra_width": rew})
+        scenes.append(([seg[b + 1] - seg[b]], [None], [False], [np.nan], None, None))
+    arrays, ncmax, _ = _paste_plan(scenes, pastes, D)
+    device = points.device
+    stream = torch.cuda.current_stream(device)
+    result_d = torch.empty(8 * B + B * ncmax, dtype=torch.uint8, device=device)
+    plan, parts = _pack(_resolve(arrays, points.data_ptr(), result_d.data_ptr() + 8 * B))
+    plan_d = torch.from_numpy(plan).to(device)
+    return _paste_run(D, parts, plan_d.data_ptr(), B, ncmax, result_d, device, stream, True)
+
+
+def append_pasted(data_dict):
+    """After the readback: the sample's gt_boxes / gt_labels with the accepted candidates' boxes and labels appended,
+    the boxes through the same BDA (bda_boxes, the parameters BevAffineTransformation left in lidar_aug["bda_params"])
+    and boxes_in_range_mask the loader applied to the scene's boxes.  -> a shallow copy of data_dict (the input is not
+    changed); the sample itself when it carries no paste record."""
+    ip = _input_prep()
+    a = data_dict.get("lidar_aug")
+    p = None if a is None else a.get("paste")
+    if p is None:
+        return data_dict
+    if "accept" not in p:
+        raise ValueError("the paste record has no accept bytes: run lidar_prep_host_clouds first")
+    scene = np.asarray(data_dict["gt_boxes"])
+    width = scene.shape[1] if scene.ndim == 2 else 7
+    db = p["database"]
+    if db.boxes.shape[1] < width:
+        raise ValueError(f"the database's boxes have {db.boxes.shape[1]} columns, the scene's {width}")
+    sel = np.nonzero(p["accept"])[0]
+    boxes = db.boxes[np.asarray(p["cand_idx"], np.int64)[sel], :width].astype(np.float32)
+    labels = np.asarray(p["cand_labels"])[sel] if "cand_labels" in p else db.class_ids[p["cand_idx"]][sel]
+    if a.get("bda_mat") is not None:
+        if a.get("bda_params") is None:
+            raise ValueError("lidar_aug has a bda_mat but no bda_params (rotate, scale, flip_dx, flip_dy) for the boxes")
+        rot, scale, fx, fy = a["bda_params"]
+        boxes = ip.bda_boxes(boxes, np.asarray(a["bda_mat"], np.float64), rot, scale, fx, fy)
+    if a.get("range") is not None and len(boxes):
+        mask = ip.boxes_in_range_mask(boxes, a["range"])
+        boxes, labels = boxes[mask], labels[mask]
+    out = dict(data_dict)
+    out["gt_boxes"] = np.concatenate([scene.reshape(-1, width), boxes]).astype(scene.dtype, copy=False)
+    if data_dict.get("gt_labels", None) is not None:
+        sl = np.asarray(data_dict["gt_labels"])
+        out["gt_labels"] = np.concatenate([sl, labels.astype(sl.dtype)])
+    return out

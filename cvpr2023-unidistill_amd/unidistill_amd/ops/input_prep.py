@@ -156,7 +156,9 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
     Samples without ``ida_aug`` draw theirs from ``ida_transform`` (an ImageAffineTransformation), camera by camera.
     A sample may carry its RAW clouds ``points_raw`` (key frame first, then its sweeps, float32 [Ni, D] arrays) with
     the ``lidar_aug`` record CollectLidarSweeps / BevAffineTransformation / ObjectRangeFilter leave in the loader:
-    ``points`` is then built by lidar_prep_host_clouds, one H2D copy and one fused pass for the batch.
+    ``points`` is then built by lidar_prep_host_clouds, one H2D copy and one fused pass for the batch.  When that record
+    holds a ``paste`` record (GTSampling, ops/gt_paste.py) the accepted database objects are pasted in the same pass
+    and their boxes / labels are appended to the sample's ``gt_boxes`` / ``gt_labels`` (images are not edited).
     A sample may carry its camera frames as JPEG files ``imgs_jpeg`` ([sweeps][cams] of bytes, nested like imgs_raw)
     with ``ida_aug`` (or an ida_transform): they are decoded on the device (ops/jpeg.py, bit-exact to Pillow) and go
     through the same image_affine launch; a frame whose decode failed raises ValueError naming sample and camera."""
@@ -181,6 +183,8 @@ def collate_fn(data, device="cuda", is_return_depth=False, with_points=True, ida
     if "points_raw" in data[0]:
         batch["points"] = lidar_prep_host_clouds([d["points_raw"] for d in data], [d.get("lidar_aug") for d in data],
                                                  device)
+        if any(d.get("lidar_aug") is not None and d["lidar_aug"].get("paste") is not None for d in data):
+            data = [append_pasted(d) for d in data]        # gt_boxes / gt_labels + the accepted candidates (§2.16)
     if "imgs_u8" in data[0]:
         u8 = torch.stack([torch.as_tensor(np.asarray(d["imgs_u8"])) for d in data]).to(device, non_blocking=True)
         batch["imgs"] = image_normalize(u8)
@@ -781,6 +785,7 @@ class BevAffineTransformation:
             if a["bda_mat"] is not None or a["range"] is not None:
                 raise ValueError("BevAffineTransformation must come once, before ObjectRangeFilter")
             a["bda_mat"] = mat
+            a["bda_params"] = (rotate, scale, flip_dx, flip_dy)      # for boxes pasted after collate (gt_paste.py)
         if data_dict.get("imgs", None) is not None:
             data_dict["bda_mat"] = mat
         return data_dict
@@ -881,16 +886,8 @@ def _plan_segments(clouds, aug, D):
     return [None] + list(mats), [False] + [True] * (n - 1), last, aug.get("bda_mat"), aug.get("range")
 
 
-def lidar_prep_host_clouds(clouds, plans, device):
-    """The reference's CollectLidarSweeps -> BevAffineTransformation -> ObjectRangeFilter on the points, then
-    collate_fn's fill_batch_tensor, for host clouds: ``clouds`` one list per sample of float32 [Ni, D] arrays (key
-    frame first, then its sweeps), ``plans`` the samples' data_dict["lidar_aug"] records (None: rows taken as they
-    are).  All clouds are packed into a pinned buffer, copied in one H2D copy and processed in one fused pass on
-    input_stream(device); the caller's current stream waits on the result.  -> float32 [B, Nmax, D] on ``device``,
-    equal to fill_batch_tensor of the reference-processed clouds bit for bit."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+def _host_clouds(clouds, plans):
+    """The samples' clouds as numpy arrays, checked.  -> (arrays per sample, D)."""
     if len(clouds) != len(plans) or not clouds:
         raise ValueError("one plan per sample, at least one sample")
     arrs = [[np.asarray(c.numpy() if torch.is_tensor(c) else c) for c in cs] for cs in clouds]
@@ -902,6 +899,25 @@ def lidar_prep_host_clouds(clouds, plans, device):
         raise ValueError("clouds must share one D >= 3")
     if any(len(cs) == 0 or len(cs) > _MAX_SEG for cs in arrs):
         raise ValueError(f"every sample needs 1 .. {_MAX_SEG} clouds")
+    return arrs, D
+
+
+def lidar_prep_host_clouds(clouds, plans, device):
+    """The reference's CollectLidarSweeps -> BevAffineTransformation -> ObjectRangeFilter on the points, then
+    collate_fn's fill_batch_tensor, for host clouds: ``clouds`` one list per sample of float32 [Ni, D] arrays (key
+    frame first, then its sweeps), ``plans`` the samples' data_dict["lidar_aug"] records (None: rows taken as they
+    are).  All clouds are packed into a pinned buffer, copied in one H2D copy and processed in one fused pass on
+    input_stream(device); the caller's current stream waits on the result.  -> float32 [B, Nmax, D] on ``device``,
+    equal to fill_batch_tensor of the reference-processed clouds bit for bit.  When a plan carries a ``paste`` record
+    (GTSampling) the batch goes through lidar_paste_host_clouds (ops/gt_paste.py), which also leaves each record's
+    ``accept`` flags in it; a batch without one takes the path below unchanged."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+    arrs, D = _host_clouds(clouds, plans)
+    if any(a is not None and a.get("paste") is not None for a in plans):      # GT sampling: DESIGN §2.16
+        return lidar_paste_host_clouds(clouds, plans, device)[0]
+    flat = [a for cs in arrs for a in cs]
     seg_rows, nseg, mats, xform, last, bdas, ranges = [], [], [], [], [], [], []
     for cs, aug in zip(arrs, plans):
         m, x, l, bda, rg = _plan_segments(cs, aug, D)
@@ -937,3 +953,8 @@ def lidar_prep_host_clouds(clouds, plans, device):
     cur.wait_event(done)
     out.record_stream(cur)
     return out
+
+
+# ---- GT-sampling (database paste) in that chain: ops/gt_paste.py ----------------------------------
+from .gt_paste import (GTSampling, ObjectDatabase, append_pasted, gt_paste,          # noqa: E402,F401
+                       lidar_paste_host_clouds)

@@ -1111,6 +1111,62 @@ int ud_depth_loss_bwd(const float* logits, int64_t sn, int64_t sc, int64_t sh, i
                       const float* result, const float* grad_out, float* dx, int64_t dn, int64_t dc, int64_t dh,
                       int64_t dw, int BN, int D, int fH, int fW, ud_stream_t stream);
 
+/* ---- GT-sampling (database paste) in the LiDAR input chain (csrc/gt_paste.hip, csrc/lidar_prep.hip) ----
+ * OpenPCDet's DataBaseSampler as the reference's GTSampling configures it (transforms3d.py:162-207), between
+ * CollectLidarSweeps and BevAffineTransformation: database objects that collide with nothing are pasted into the scene,
+ * the scene's points inside their (enlarged) boxes are removed.
+ *   ud_gt_paste_select   Per sample b: scene boxes gt f32 [gt_off[b] .. gt_off[b+1])[7] (x, y, z, dx, dy, dz, yaw; before
+ *                        BDA), candidates cand f32 [cand_off[b] .. cand_off[b+1])[7] with cand_group i32 (ascending; a
+ *                        group is a run of equal ids), at most UD_GT_PASTE_MAX_CAND per sample.  accept u8
+ *                        [B][accept_stride] (accept_stride >= every sample's candidates; bytes past them are 0).  Groups
+ *                        in order; a candidate is accepted iff its rotated-BEV IoU (ud_boxes_iou_bev's arithmetic) is
+ *                        exactly 0 with every scene box, with every ACCEPTED candidate of an earlier group and with every
+ *                        OTHER candidate of its own group (two colliding candidates of a group are both dropped; not a
+ *                        greedy NMS).  A candidate with a non-finite entry is rejected and blocks nobody; a non-finite
+ *                        scene box collides with nobody.  One workgroup per sample, one launch, no atomics; the offsets
+ *                        are given on the host (validation) and on the device.
+ *   ud_lidar_paste_count / ud_lidar_paste_compact   ud_lidar_prep_count / _compact (same plan, same kernels, same
+ *                        workspace and output contract) with, per segment, seg_paste[s] (device, or NULL for none):
+ *                          src    the segment's rows are read from src (row 0 = the segment's first) instead of pts;
+ *                                 pts may be NULL when every segment has one (rows = seg_host[S] then);
+ *                          gate   when not NULL and *gate == 0 every row of the segment is dropped;
+ *                          object != 0: an object segment, never tested against the removal boxes;
+ *                        and per sample the removal boxes rm_boxes f32 [rm_off[b] .. rm_off[b+1])[7] (at most
+ *                        UD_GT_PASTE_MAX_CAND; rm_off NULL on host and device: none), box j active when
+ *                        rm_accept[b * rm_stride + j] != 0.  A row of a scene segment is dropped when its float32
+ *                        position after the segment transform, BEFORE the BDA, lies inside an active box:
+ *                          sx = x - cx, sy = y - cy;   |z - cz| <= dz / 2;
+ *                          lx = sx * cos(yaw) + sy * sin(yaw),   ly = -sx * sin(yaw) + sy * cos(yaw);
+ *                          |lx| < dx / 2 + 1e-5  and  |ly| < dy / 2 + 1e-5
+ *                        all in float32 (OpenPCDet's check_pt_in_box3d).  BDA, range test, stable compaction and both
+ *                        output layouts are those of ud_lidar_prep_*, for object rows too.  Object clouds are ordinary
+ *                        segments placed ahead of the key frame: gate = the candidate's accept byte, matrix = the
+ *                        translation by its box centre (database clouds are box-centred), last = NaN.
+ *                        UD_ERR_INVALID_ARG, nothing launched: everything ud_lidar_prep_* rejects (more than
+ *                        UD_LIDAR_MAX_SEGMENTS segments in a sample: 1 + sweeps + candidates > 64), more than
+ *                        UD_GT_PASTE_MAX_CAND removal boxes in a sample, rm_stride below a sample's boxes. */
+#define UD_GT_PASTE_MAX_CAND 63
+typedef struct {
+  const float* src;
+  const uint8_t* gate;
+  int64_t object;
+} UdLidarPasteSeg;
+int ud_gt_paste_select(const float* gt, const int64_t* gt_off_host, const int64_t* gt_off_dev, const float* cand,
+                       const int32_t* cand_group, const int64_t* cand_off_host, const int64_t* cand_off_dev, int B,
+                       uint8_t* accept, int64_t accept_stride, ud_stream_t stream);
+int ud_lidar_paste_count(const float* pts, int64_t rows, int D, const int64_t* seg_host, const int64_t* sample_seg_host,
+                         int S, int B, const int64_t* seg_dev, const int64_t* sample_seg_dev, const double* seg_par,
+                         const double* smp_par, const UdLidarPasteSeg* seg_paste, const float* rm_boxes,
+                         const int64_t* rm_off_host, const int64_t* rm_off_dev, const uint8_t* rm_accept,
+                         int64_t rm_stride, int64_t* counts, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+int ud_lidar_paste_compact(const float* pts, int64_t rows, int D, const int64_t* seg_host,
+                           const int64_t* sample_seg_host, int S, int B, const int64_t* seg_dev,
+                           const int64_t* sample_seg_dev, const double* seg_par, const double* smp_par,
+                           const UdLidarPasteSeg* seg_paste, const float* rm_boxes, const int64_t* rm_off_host,
+                           const int64_t* rm_off_dev, const uint8_t* rm_accept, int64_t rm_stride,
+                           const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact, float* out,
+                           int64_t out_rows, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
