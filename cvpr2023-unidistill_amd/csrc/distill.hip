@@ -265,12 +265,14 @@ __global__ __launch_bounds__(256) void k_rel(MapView s, MapView t, const float* 
 // cold GPUs).  Here every (m, kp, i) term of a sample gets the key (pixel, term index); the keys of a sample are sorted,
 // runs of equal pixels are found, and a lane (= channel) adds the terms of a pixel in term order and stores the pixel
 // once -- no atomics, fixed order.  Two sorters, chosen by the number of terms T = 36 * M (M = padded box count):
-//   * T <= 16384 (M <= 455): bitonic sort in LDS (dynamic, 10 bytes per term), repeated by the (64 channels, 1/8 of the
-//     runs) workgroups of a sample, which is cheaper than a second launch;
+//   * T <= 8192 (M <= 227): bitonic sort in LDS (dynamic, 10 bytes per term), repeated by the (64 channels, 1/8 of the
+//     runs) workgroups of a sample, which is cheaper than a second launch.  (16384 terms do NOT fit: 10 bytes per term are
+//     the whole 160 KiB of a CU, and the end-of-runs entry plus the kernel's static LDS come on top, so that launch was
+//     refused by the runtime for every M in 228..455);
 //   * larger: rank sort through the workspace (every key is unique, so its rank = the number of smaller keys; O(T^2)
 //     compares, no size limit), then one pass over the sorted keys.
 constexpr int kMinTerms = 2048;                // 8 sorted entries per thread at least
-constexpr int kMaxLdsTerms = 16384;            // 160 KB of LDS would hold 16384 * 10 bytes
+constexpr int kMaxLdsTerms = 8192;             // 80 KB + 16 bytes of dynamic LDS; the next size, 16384, needs more than a CU has
 constexpr int kRunSplit = 8;                   // workgroups sharing the pixels of one (sample, 64 channels)
 
 __device__ __forceinline__ bool term_pixel(const float* __restrict__ corners, const unsigned char* __restrict__ valid,
