@@ -192,6 +192,14 @@ def require_gpu(*tensors):
                                f"got a tensor on {t.device}")
 
 
+def require_gpu_device(device):
+    """torch.device(device), which must be a GPU."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+    return device
+
+
 _workspaces = {}
 _scope = ["eager"]
 

@@ -12,13 +12,10 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import lidar_prep as lp
+from .staging import align16, staged_upload
 
 MAX_CAND = 63            # include/unidistill_hip.h UD_GT_PASTE_MAX_CAND
-
-
-def _input_prep():
-    from . import input_prep          # imported late: input_prep re-exports this module's names
-    return input_prep
 
 
 def _parse_cfg(entries):
@@ -196,7 +193,7 @@ class GTSampling:
             return data_dict
         if data_dict.get("points", None) is None:
             return data_dict
-        a = _input_prep()._lidar_aug(data_dict)
+        a = lp._lidar_aug(data_dict)
         if a.get("bda_mat") is not None or a.get("range") is not None:
             raise ValueError("GTSampling must come before BevAffineTransformation and ObjectRangeFilter")
         counts = self._scene_counts(data_dict) if self.limit_whole_scene else None
@@ -218,41 +215,25 @@ class GTSampling:
                       "remove_extra_width": self.remove_extra_width}
         return data_dict
 
-    def __call__(self, data_dict):
-        return self.forward(data_dict)
+    __call__ = forward
 
 
 def check_segments(sweeps, candidates, sample=None):
     """The chain takes UD_LIDAR_MAX_SEGMENTS = 64 segments per sample: key frame + sweeps + candidates."""
-    ip = _input_prep()
     where = "" if sample is None else f"sample {sample}: "
     if candidates > MAX_CAND:
         raise ValueError(f"{where}{candidates} candidates, the device selection takes at most {MAX_CAND}")
-    if 1 + sweeps + candidates > ip._MAX_SEG:
+    if 1 + sweeps + candidates > lp._MAX_SEG:
         raise ValueError(f"{where}1 key frame + {sweeps} sweeps + {candidates} candidates = "
-                         f"{1 + sweeps + candidates} segments, the chain takes at most {ip._MAX_SEG}")
-
-
-def _pack(arrays):
-    """[(name, array)] -> (uint8 buffer with 16-byte aligned sections, {name: (offset, array)})."""
-    ip = _input_prep()
-    parts, off = {}, 0
-    for name, a in arrays:
-        parts[name] = (off, a)
-        off = ip._align16(off + a.nbytes)
-    buf = np.zeros(max(off, 16), np.uint8)
-    for o, a in parts.values():
-        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    return buf, parts
+                         f"{1 + sweeps + candidates} segments, the chain takes at most {lp._MAX_SEG}")
 
 
 def _paste_plan(scenes, pastes, D):
     """Host plan of a paste batch.  scenes: per sample (rows per scene segment, matrices, transform flags, last-column
     values, BDA, range) as _plan_segments gives them; pastes: per sample the paste record or None.  Object segments go
-    ahead of the sample's scene segments.  -> (arrays in plan order with the pointers still relative, ncmax, scene rows); the
-    ``pseg`` rows are (src, gate, object): src of an object segment is absolute (the database), src of a scene segment
-    is the byte offset of its first row inside the scene buffer, gate the byte offset inside the accept block."""
-    ip = _input_prep()
+    ahead of the sample's scene segments.  -> (packed plan with the pointers still relative, its parts, ncmax, scene
+    rows); the ``pseg`` rows are (src, gate, object): src of an object segment is absolute (the database), src of a scene
+    segment is the byte offset of its first row inside the scene buffer, gate the byte offset inside the accept block."""
     B = len(scenes)
     ncs = [0 if p is None else len(p["cand_idx"]) for p in pastes]
     for b, ((rows, *_), nc) in enumerate(zip(scenes, ncs)):
@@ -294,64 +275,38 @@ def _paste_plan(scenes, pastes, D):
         last += list(l)
         bdas.append(bda)
         ranges.append(rg)
-    _, base = ip._lidar_tables(seg_rows, nseg, mats, xform, last, bdas, ranges)
     cat = lambda xs, w, dt: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros((0,) + w, dt), dt)
     off = lambda ns: np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
-    arrays = [(k, base[k][1]) for k in ("seg", "sseg", "seg_par", "smp_par")]
+    arrays = lp._lidar_arrays(seg_rows, nseg, mats, xform, last, bdas, ranges)
     arrays += [("pseg", np.array(pseg, np.int64).reshape(-1, 3)), ("gt", cat(gts, (7,), np.float32)),
                ("gt_off", off([len(g) for g in gts])), ("cand", cat(cands, (7,), np.float32)),
                ("cand_off", off(ncs)), ("cand_group", cat(groups, (), np.int32)), ("rm", cat(rms, (7,), np.float32))]
-    return arrays, ncmax, scene_row
+    return (*lp._pack(arrays), ncmax, scene_row)
 
 
-def _resolve(arrays, scene_ptr, accept_ptr):
-    """Turns the relative pointers of ``pseg`` into addresses (gate 0 = no gate; stored offsets are 1-based)."""
-    out = []
-    for name, a in arrays:
-        if name == "pseg":
-            a = a.copy()
-            scene = a[:, 2] == 0
-            a[scene, 0] += scene_ptr
-            a[~scene, 1] += accept_ptr - 1
-        out.append((name, a))
-    return out
+def _resolve(plan, parts, scene_ptr, accept_ptr):
+    """Turns the relative pointers of the packed plan's ``pseg`` section into addresses, in place (gate 0 = no gate;
+    stored offsets are 1-based)."""
+    o, a = parts["pseg"]
+    pseg = plan[o:o + a.nbytes].view(np.int64).reshape(-1, 3)
+    scene = pseg[:, 2] == 0
+    pseg[scene, 0] += scene_ptr
+    pseg[~scene, 1] += accept_ptr - 1
 
 
 def _paste_run(D, parts, plan_base, B, ncmax, result_d, device, stream, out_compact):
-    """ud_gt_paste_select -> ud_lidar_paste_count -> ONE readback of [counts | accept bytes] (waits on ``stream``
-    only) -> ud_lidar_paste_compact, all on ``stream`` (current while this runs).
-    -> (out, counts int64 numpy [B], accept uint8 numpy [B, ncmax])."""
-    lib = _lib.load()
-    seg, sseg = parts["seg"][1], parts["sseg"][1]
+    """ud_gt_paste_select, then the chain's two passes (lidar_prep._two_pass) with ud_lidar_paste_count /
+    ud_lidar_paste_compact: ONE readback of ``result_d`` = [counts | accept bytes], all on ``stream`` (current while
+    this runs).  -> (out, counts int64 numpy [B], accept uint8 numpy [B, ncmax])."""
     gt_off, cand_off = parts["gt_off"][1], parts["cand_off"][1]
-    S = len(seg) - 1
-    rows = int(seg[-1])
-    p = {k: plan_base + o for k, (o, _) in parts.items()}
-    ws_bytes = int(lib.ud_lidar_prep_workspace_bytes(seg.ctypes.data, sseg.ctypes.data, S, B))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
-    hs = stream.cuda_stream
-    counts_ptr, accept_ptr = result_d.data_ptr(), result_d.data_ptr() + 8 * B
+    args, ws, p = lp._chain_setup(None, int(parts["seg"][1][-1]), D, parts, plan_base, device)
+    accept_ptr = result_d.data_ptr() + 8 * B
     _lib.ud.ud_gt_paste_select(p["gt"], gt_off.ctypes.data, p["gt_off"], p["cand"], p["cand_group"],
-                               cand_off.ctypes.data, p["cand_off"], B, accept_ptr, ncmax, hs)
-    args = (None, rows, D, seg.ctypes.data, sseg.ctypes.data, S, B, p["seg"], p["sseg"], p["seg_par"], p["smp_par"],
-            p["pseg"], p["rm"], cand_off.ctypes.data, p["cand_off"], accept_ptr, ncmax)
-    _lib.ud.ud_lidar_paste_count(*args, counts_ptr, ws, ws_bytes, hs)
-    result_h = torch.empty(result_d.numel(), dtype=torch.uint8, pin_memory=True)
-    result_h.copy_(result_d, non_blocking=True)         # counts and accept bytes: one copy, one event
-    ev = torch.cuda.Event()
-    ev.record(stream)
-    ev.synchronize()
-    rh = result_h.numpy()
-    counts = rh[:8 * B].view(np.int64).copy()
-    accept = rh[8 * B:8 * B + B * ncmax].reshape(B, ncmax).copy()
-    nmax = int(counts.max()) if B else 0
-    if out_compact:
-        out = torch.empty((int(counts.sum()), D), dtype=torch.float32, device=device)
-    else:
-        out = torch.empty((B, nmax, D), dtype=torch.float32, device=device)
-    _lib.ud.ud_lidar_paste_compact(*args, counts.ctypes.data, counts_ptr, nmax, 1 if out_compact else 0, out,
-                                   out.numel() // D, ws, ws_bytes, hs)
-    return out, counts, accept
+                               cand_off.ctypes.data, p["cand_off"], B, accept_ptr, ncmax, stream.cuda_stream)
+    args += (p["pseg"], p["rm"], cand_off.ctypes.data, p["cand_off"], accept_ptr, ncmax)
+    out, counts, accept = lp._two_pass(_lib.ud.ud_lidar_paste_count, _lib.ud.ud_lidar_paste_compact, args, result_d, ws,
+                                       device, stream, out_compact)
+    return out, counts, accept.reshape(B, ncmax).copy()
 
 
 def _store_accept(pastes, accept):
@@ -366,44 +321,28 @@ def lidar_paste_host_clouds(clouds, plans, device, compact=False):
     sample's scene (concatenate([obj_points, points])), BDA / range filter / padding as without paste.  One H2D copy
     (scene clouds + plan), four launches, one host wait.  Each paste record gets ``accept`` (bool per candidate).
     -> (points f32 [B, Nmax, D], or [sum(counts), D] with ``compact``; counts int64 [B]; accept uint8 [B, Ncmax])."""
-    ip = _input_prep()
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
-    arrs, D = ip._host_clouds(clouds, plans)
+    device = _lib.require_gpu_device(device)
+    arrs, D = lp._host_clouds(clouds, plans)
     pastes = [None if a is None else a.get("paste") for a in plans]
     scenes = []
     for cs, aug in zip(arrs, plans):
-        m, x, l, bda, rg = ip._plan_segments(cs, aug, D)
+        m, x, l, bda, rg = lp._plan_segments(cs, aug, D)
         scenes.append(([len(a) for a in cs], m, x, l, bda, rg))
-    arrays, ncmax, rows = _paste_plan(scenes, pastes, D)
+    plan, parts, ncmax, rows = _paste_plan(scenes, pastes, D)
     B = len(arrs)
-    plan_bytes = len(_pack(arrays)[0])
-    pts_bytes = ip._align16(rows * D * 4)
-    i = ip._device_index(device)
-    device = torch.device("cuda", i)
-    host, copied = ip._staging(i, pts_bytes + plan_bytes)
-    hv = host.numpy()
-    fv = hv[:rows * D * 4].view(np.float32)
-    off = 0
-    for cs in arrs:
-        for a in cs:
-            fv[off:off + a.size] = a.reshape(-1)
-            off += a.size
-    cur = torch.cuda.current_stream(device)
-    s = ip.input_stream(device)
-    with torch.cuda.stream(s):
-        dev = torch.empty(pts_bytes + plan_bytes, dtype=torch.uint8, device=device)
-        result_d = torch.empty(8 * B + B * ncmax, dtype=torch.uint8, device=device)
-        plan, parts = _pack(_resolve(arrays, dev.data_ptr(), result_d.data_ptr() + 8 * B))
-        hv[pts_bytes:pts_bytes + plan_bytes] = plan
-        dev.copy_(host[:dev.numel()], non_blocking=True)
-        copied.record(s)
-        out, counts, accept = _paste_run(D, parts, dev.data_ptr() + pts_bytes, B, ncmax, result_d, device, s, compact)
-        done = torch.cuda.Event()
-        done.record(s)
-    cur.wait_event(done)
-    out.record_stream(cur)
+    pts_bytes = align16(rows * D * 4)
+    result = []
+
+    def fill(host, dev):                    # the plan holds addresses inside dev and result_d
+        result.append(torch.empty(8 * B + B * ncmax, dtype=torch.uint8, device=dev.device))
+        lp._stage_clouds(host, arrs)
+        _resolve(plan, parts, dev.data_ptr(), result[0].data_ptr() + 8 * B)
+        host[pts_bytes:] = plan
+
+    def run(dev, s):
+        return _paste_run(D, parts, dev.data_ptr() + pts_bytes, B, ncmax, result[0], dev.device, s, compact)
+
+    out, counts, accept = staged_upload(device, pts_bytes + len(plan), fill, run)
     _store_accept(pastes, accept)
     return out, counts, accept
 
@@ -415,13 +354,8 @@ def gt_paste(points, seg, gt_boxes, database, cand_idx, cand_group, remove_extra
     points inside an accepted candidate's box (enlarged by ``remove_extra_width``) are dropped, the accepted objects'
     clouds are placed ahead of their sample's scene.  No sweep transform, BDA or range filter.  Runs on the current
     stream; one host wait.  -> (points_out f32 [sum(counts), D], counts int64 numpy [B], accept uint8 numpy [B, Ncmax])."""
-    _lib.require_gpu(points)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous():
-        raise ValueError("points must be a contiguous float32 [rows, D >= 3] tensor")
-    rows, D = points.shape
-    seg = [int(v) for v in seg]
-    if len(seg) < 2 or seg[0] != 0 or seg[-1] != rows or any(b < a for a, b in zip(seg, seg[1:])):
-        raise ValueError("seg must ascend from 0 to the number of rows")
+    seg = lp._check_points_seg(points, seg, 2)
+    D = points.shape[1]
     B = len(seg) - 1
     if B == 1 and not isinstance(cand_idx, (list, tuple)):
         gt_boxes, cand_idx, cand_group = [gt_boxes], [cand_idx], [cand_group]
@@ -437,11 +371,11 @@ def gt_paste(points, seg, gt_boxes, database, cand_idx, cand_group, remove_extra
                        "gt_boxes": np.asarray(gt_boxes[b], np.float32),
                        "remove_extra_width": rew})
         scenes.append(([seg[b + 1] - seg[b]], [None], [False], [np.nan], None, None))
-    arrays, ncmax, _ = _paste_plan(scenes, pastes, D)
+    plan, parts, ncmax, _ = _paste_plan(scenes, pastes, D)
     device = points.device
     stream = torch.cuda.current_stream(device)
     result_d = torch.empty(8 * B + B * ncmax, dtype=torch.uint8, device=device)
-    plan, parts = _pack(_resolve(arrays, points.data_ptr(), result_d.data_ptr() + 8 * B))
+    _resolve(plan, parts, points.data_ptr(), result_d.data_ptr() + 8 * B)
     plan_d = torch.from_numpy(plan).to(device)
     return _paste_run(D, parts, plan_d.data_ptr(), B, ncmax, result_d, device, stream, True)
 
@@ -451,7 +385,6 @@ def append_pasted(data_dict):
     the boxes through the same BDA (bda_boxes, the parameters BevAffineTransformation left in lidar_aug["bda_params"])
     and boxes_in_range_mask the loader applied to the scene's boxes.  -> a shallow copy of data_dict (the input is not
     changed); the sample itself when it carries no paste record."""
-    ip = _input_prep()
     a = data_dict.get("lidar_aug")
     p = None if a is None else a.get("paste")
     if p is None:
@@ -470,9 +403,9 @@ def append_pasted(data_dict):
         if a.get("bda_params") is None:
             raise ValueError("lidar_aug has a bda_mat but no bda_params (rotate, scale, flip_dx, flip_dy) for the boxes")
         rot, scale, fx, fy = a["bda_params"]
-        boxes = ip.bda_boxes(boxes, np.asarray(a["bda_mat"], np.float64), rot, scale, fx, fy)
+        boxes = lp.bda_boxes(boxes, np.asarray(a["bda_mat"], np.float64), rot, scale, fx, fy)
     if a.get("range") is not None and len(boxes):
-        mask = ip.boxes_in_range_mask(boxes, a["range"])
+        mask = lp.boxes_in_range_mask(boxes, a["range"])
         boxes, labels = boxes[mask], labels[mask]
     out = dict(data_dict)
     out["gt_boxes"] = np.concatenate([scene.reshape(-1, width), boxes]).astype(scene.dtype, copy=False)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .staging import align16, device_index, staged_upload
 
 OK, UNSUPPORTED, TRUNCATED, CORRUPT = 0, 1, 2, 3           # UD_JPEG_* (include/unidistill_hip.h)
 ST_MARKER, ST_CODE, ST_LENGTH = 1, 2, 4                    # UD_JPEG_ST_* status bits
@@ -82,10 +83,6 @@ def _pillow_decode(index, data):
         raise JpegFrameError(index, f"unsupported by the device decoder and Pillow failed: {e}") from e
 
 
-def _round16(n):
-    return (n + 15) // 16 * 16
-
-
 def jpeg_decode(buffers, device, out=None):
     """Decode host JPEG files (``bytes`` or 1-D uint8 arrays) on ``device`` -> (frames uint8 [N, H, W, 3], status
     int32 [N]), both on the device.  The frames must share H x W (ValueError otherwise).  A status word is 0 or the
@@ -93,10 +90,7 @@ def jpeg_decode(buffers, device, out=None):
     with it.  Runs on input_stream(device); the caller's current stream waits on the result.  ``out``: an optional
     uint8 [N, H, W, 3] device tensor to decode into; the decode is ordered after the work already queued on the
     caller's current stream.  A file that cannot be decoded at all raises JpegFrameError (ValueError) with its index."""
-    from .input_prep import _device_index, _staging, input_stream
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("unidistill_amd ops run on the GPU only (no CPU fallback); got device " + str(device))
+    device = _lib.require_gpu_device(device)
     datas = [_as_bytes(b) for b in buffers]
     if not datas:
         raise ValueError("no JPEG frames")
@@ -115,7 +109,7 @@ def jpeg_decode(buffers, device, out=None):
     H, W = sizes.pop()
     N, fb = len(datas), H * W * 3
     if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous()
-                            or out.device != torch.device("cuda", _device_index(device))):
+                            or out.device != torch.device("cuda", device_index(device))):
         raise ValueError(f"out must be a contiguous uint8 [{N}, {H}, {W}, 3] tensor on {device}")
 
     # host staging: files, then Pillow's frames for the fallback, then the records
@@ -124,12 +118,12 @@ def jpeg_decode(buffers, device, out=None):
     for i, rec in recs:
         file_off.append(off)
         rec.src_off = off
-        off = _round16(off + len(datas[i]))
+        off = align16(off + len(datas[i]))
     src_bytes = off
     host_off = {}
     for i in host_frames:
         host_off[i] = off
-        off = _round16(off + fb)
+        off = align16(off + fb)
     rec_arr = (UdJpegFrame * max(len(recs), 1))(*[r for _, r in recs])
     ws_bytes = int(lib.ud_jpeg_plan(rec_arr, len(recs))) if recs else 0
     if recs and ws_bytes == 0:
@@ -138,24 +132,18 @@ def jpeg_decode(buffers, device, out=None):
         rec_arr[j].out_off = i * fb                        # the frame's slot in out
     rec_off = off
     rec_bytes = ctypes.sizeof(rec_arr) if recs else 0
-    total = rec_off + rec_bytes
-    i_dev = _device_index(device)
-    device = torch.device("cuda", i_dev)
-    host, copied = _staging(i_dev, total)
-    hv = host.numpy()
-    for (i, _), o in zip(recs, file_off):
-        hv[o:o + len(datas[i])] = np.frombuffer(datas[i], np.uint8)
-    for i, a in host_frames.items():
-        hv[host_off[i]:host_off[i] + fb] = np.ascontiguousarray(a, np.uint8).reshape(-1)
-    if rec_bytes:
-        ctypes.memmove(hv.ctypes.data + rec_off, rec_arr, rec_bytes)
+    cur = None if out is None else torch.cuda.current_stream(device)
 
-    cur = torch.cuda.current_stream(device)
-    s = input_stream(device)
-    with torch.cuda.stream(s):
-        dev = torch.empty(total, dtype=torch.uint8, device=device)
-        dev.copy_(host[:total], non_blocking=True)
-        copied.record(s)
+    def fill(hv, dev):
+        for (i, _), o in zip(recs, file_off):
+            hv[o:o + len(datas[i])] = np.frombuffer(datas[i], np.uint8)
+        for i, a in host_frames.items():
+            hv[host_off[i]:host_off[i] + fb] = np.ascontiguousarray(a, np.uint8).reshape(-1)
+        if rec_bytes:
+            ctypes.memmove(hv.ctypes.data + rec_off, rec_arr, rec_bytes)
+
+    def run(dev, s, out=out):
+        device = dev.device
         if out is None:
             out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=device)
         else:
@@ -176,11 +164,9 @@ def jpeg_decode(buffers, device, out=None):
             idx = torch.tensor([i for i, _ in recs], dtype=torch.int64).to(device, non_blocking=True)
             status.index_copy_(0, idx, st_d[:len(recs)])
             iters.index_copy_(0, idx, st_d[len(recs):])
-        done = torch.cuda.Event()
-        done.record(s)
-    cur.wait_event(done)
-    for t in (out, status, iters):
-        t.record_stream(cur)
+        return out, status, iters
+
+    out, status, iters = staged_upload(device, rec_off + rec_bytes, fill, run)
     STATS["frames"] += len(recs)
     STATS["fallback"] += len(host_frames)
     STATS["last_sync_iters"] = iters

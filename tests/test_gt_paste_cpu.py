@@ -14,6 +14,7 @@ import gt_paste_reference as ref                                                
 
 from unidistill_amd.ops import gt_paste as gp                                       # noqa: E402  (absent before this feature)
 from unidistill_amd.ops import input_prep as ip                                     # noqa: E402
+from unidistill_amd.ops import lidar_prep as lp                                     # noqa: E402
 
 NAMES = ["car", "truck", "bicycle", "bus"]
 
@@ -166,7 +167,7 @@ def test_more_than_64_segments_is_a_value_error_naming_the_numbers():
            "paste": {"database": db, "cand_idx": np.arange(55), "cand_group": np.zeros(55, np.int32),
                      "gt_boxes": np.zeros((0, 7), np.float32), "remove_extra_width": (0, 0, 0)}}
     with pytest.raises(ValueError, match=r"1 key frame \+ 9 sweeps \+ 55 candidates = 65"):
-        gp._paste_plan([([2] * 10, *ip._plan_segments(cs, aug, 5))], [aug["paste"]], 5)
+        gp._paste_plan([([2] * 10, *lp._plan_segments(cs, aug, 5))], [aug["paste"]], 5)
     with pytest.raises(ValueError, match="64 candidates"):
         gp.check_segments(0, 64)
     gp.check_segments(9, 54)                                                        # 64 segments: fine

@@ -213,7 +213,7 @@ def test_collate_end_to_end_and_the_voxelizer_takes_the_batch(world):
 def test_batch_without_a_paste_record_is_the_existing_path(world):
     """collate_fn on samples that never saw GTSampling: torch.equal to ud_lidar_prep_* driven directly (the existing
     route), and the boxes / labels are the samples' own."""
-    from unidistill_amd.ops import input_prep as ip
+    from unidistill_amd.ops import input_prep as ip, lidar_prep as lp
     data = _samples(world, False)
     assert all("paste" not in d["lidar_aug"] for d in data)
     batch = ip.collate_fn(data, device=DEV)
@@ -221,16 +221,16 @@ def test_batch_without_a_paste_record_is_the_existing_path(world):
     D = 5
     rows, nseg, mats, xf, last, bdas, rgs = [], [], [], [], [], [], []
     for cs, a in zip(clouds, plans):
-        m, x, l, bda, rg = ip._plan_segments(cs, a, D)
+        m, x, l, bda, rg = lp._plan_segments(cs, a, D)
         rows += [len(c) for c in cs]
         nseg.append(len(cs))
         mats, xf, last = mats + m, xf + x, last + l
         bdas.append(bda)
         rgs.append(rg)
-    buf, parts = ip._lidar_tables(rows, nseg, mats, xf, last, bdas, rgs)
+    buf, parts = lp._lidar_tables(rows, nseg, mats, xf, last, bdas, rgs)
     x = torch.from_numpy(np.concatenate([c for cs in clouds for c in cs])).to(DEV)
     plan = torch.from_numpy(buf).to(DEV)
-    want, _ = ip._lidar_run(x, x.shape[0], D, parts, plan.data_ptr(), torch.device(DEV), torch.cuda.current_stream(),
+    want, _ = lp._lidar_run(x, x.shape[0], D, parts, plan.data_ptr(), torch.device(DEV), torch.cuda.current_stream(),
                             False)
     torch.cuda.synchronize()
     assert torch.equal(batch["points"].view(torch.int32), want.view(torch.int32))

@@ -172,14 +172,14 @@ def test_rotation_constants_and_tables_properties():
 
 
 def test_bad_inputs_raise():
-    from unidistill_amd.ops import input_prep as ip
+    from unidistill_amd.ops import image_affine, input_prep as ip
     good = (0.44, (704, 396), (0, 140, 704, 396), False, 0.0)
     with pytest.raises(RuntimeError, match="GPU only"):
         ip.image_affine(torch.zeros(900, 1600, 3, dtype=torch.uint8), [good])
     with pytest.raises(ValueError):                                                  # wrong crop size
         ip.plan_frames([(0.44, (704, 396), (0, 140, 700, 396), False, 0.0)], 900, 1600, (256, 704), torch.device("cpu"))
     with pytest.raises(ValueError):                                                  # not an augs tuple
-        ip._flat_augs([1, 2, 3])
+        image_affine._flat_augs([1, 2, 3])
     with pytest.raises(ValueError):
         ip.resample_table(0, 5)
     with pytest.raises(ValueError):                                                  # host frames: dtype / shape
@@ -197,10 +197,10 @@ def test_bad_inputs_raise():
 def test_launcher_rejects_bad_records(hip_lib):
     """ud_image_affine's bounds check of the records is a pure host function (ud_image_affine_check, which the launcher
     runs before it launches anything): called here directly, so nothing can reach a kernel."""
-    from unidistill_amd.ops import input_prep as ip
+    from unidistill_amd.ops import image_affine, input_prep as ip
     recs, bands, _ = ip.plan_frames([(0.44, (704, 396), (0, 140, 704, 396), False, 0.0)], 900, 1600, (256, 704),
                                     torch.device("cpu"))
-    i = ip._FRAME_FIELDS.index
+    i = image_affine._FRAME_FIELDS.index
     recs[0, i("src_rows")] = 900
     ws_bytes = hip_lib.ud_image_affine_workspace_bytes(recs.ctypes.data, 1)
     assert ws_bytes >= bands[0][1] * 704 * 3 and ws_bytes == hip_lib.ud_image_affine_workspace_bytes(recs.ctypes.data, 1)

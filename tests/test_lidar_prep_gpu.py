@@ -212,3 +212,32 @@ def test_distill_step_same_losses_both_routes(hip_lib, golden):
     for k in losses[0]:
         assert torch.equal(losses[0][k], losses[1][k]), k
         assert torch.isfinite(losses[0][k]).all(), k
+
+
+def test_staged_upload_reuse_regrowth_and_stream_order(hip_lib):
+    """ops/staging.py staged_upload with byte payloads and no kernel: 4 KiB, then 2 KiB of other bytes through the same
+    pinned buffer (reuse), then 1 MiB + 16 (the buffer grows past its 1 MiB floor), each issued while the caller's
+    non-default stream has a fill pending; once that stream is synchronised the device bytes are the host bytes."""
+    from unidistill_amd.ops import staging
+    dev = torch.device(DEV)
+    torch.cuda.synchronize()
+    staging._buffers.pop(dev.index, None)                   # start below the floor whatever ran before in this process
+    rng = np.random.default_rng(11)
+    side = torch.cuda.Stream(device=dev)
+    sent, sizes = [], []
+    with torch.cuda.stream(side):
+        for n in (4096, 2048, (1 << 20) + 16):
+            payload = rng.integers(0, 256, n, dtype=np.uint8)
+            torch.empty(1 << 20, dtype=torch.uint8, device=dev).fill_(n % 251)      # pending on the caller's stream
+
+            def fill(host, d, payload=payload):
+                assert host.shape == (n,) and d.numel() == n
+                host[:] = payload
+            up, = staging.staged_upload(dev, n, fill, lambda d, s: (d,))
+            sent.append((payload, up, up.clone()))          # the clone runs on the caller's stream, behind the wait
+            sizes.append(staging._buffers[dev.index][0].numel())
+        side.synchronize()
+    assert sizes == [1 << 20, 1 << 20, (1 << 20) + 16]
+    for payload, up, copy in sent:
+        want = torch.from_numpy(payload)
+        assert torch.equal(up.cpu(), want) and torch.equal(copy.cpu(), want)

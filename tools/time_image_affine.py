@@ -12,7 +12,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "cvpr2023-unidistill_amd")]
 import numpy as np
 import torch
 
-from unidistill_amd.ops import input_prep as ip
+from unidistill_amd.ops import image_affine, input_prep as ip
 
 COPY_TBS = 6.3                                   # measured device copy rate (DESIGN)
 B, NCAM = int(os.environ.get("B", 4)), int(os.environ.get("NCAM", 6))
@@ -41,7 +41,7 @@ def timeit(fn, n=ITERS):
 
 
 recs, bands, _ = ip.plan_frames(augs, 900, 1600, (256, 704), d)
-i = ip._FRAME_FIELDS.index
+i = image_affine._FRAME_FIELDS.index
 band_rows = sum(r for _, r in bands)
 src_bytes = sum(int(r[i("band_rows")]) * 1600 * 3 for r in recs)              # source rows the kernel reads
 mid_bytes = sum(int(r[i("band_rows")]) * int(r[i("ncols")]) * 3 for r in recs)  # uint8 intermediate, written + read
