@@ -128,20 +128,20 @@ inline int ud_bn_bwd_final(const float* partial, int slices, int C, long long P,
   return UD_OK;
 }
 
-// out[c] = sum over the slices of partial[slice][c]
-template <int T>
-__global__ __launch_bounds__(T) void k_colsum_final(const float* __restrict__ partial, int slices, int C, float* __restrict__ out) {
-  __shared__ float red[T / 64];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;      // T threads per channel, fixed-order reduction
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+// Sum over the slices of partial[slice][c] by a workgroup of T threads, in V: thread t adds slices t, t + T, ... with four
+// independent loads in flight, then a fixed tree.  The total is valid on thread 0; red holds T / 64 values.
+template <int T, typename V>
+__device__ __forceinline__ V ud_colsum_block(const V* __restrict__ partial, int slices, int C, int c, V* __restrict__ red) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;      // T threads per channel, fixed-order reduction
+  V a0 = 0, a1 = 0, a2 = 0, a3 = 0;
   int s = tid;
   for (; s + 3 * T < slices; s += 4 * T) {
-    const float v0 = partial[(size_t)s * C + c], v1 = partial[(size_t)(s + T) * C + c], v2 = partial[(size_t)(s + 2 * T) * C + c],
-                v3 = partial[(size_t)(s + 3 * T) * C + c];
+    const V v0 = partial[(size_t)s * C + c], v1 = partial[(size_t)(s + T) * C + c], v2 = partial[(size_t)(s + 2 * T) * C + c],
+            v3 = partial[(size_t)(s + 3 * T) * C + c];
     a0 += v0; a1 += v1; a2 += v2; a3 += v3;
   }
   for (; s < slices; s += T) a0 += partial[(size_t)s * C + c];
-  float a = (a0 + a1) + (a2 + a3);
+  V a = (a0 + a1) + (a2 + a3);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
   if (T > 64) {
@@ -153,12 +153,39 @@ __global__ __launch_bounds__(T) void k_colsum_final(const float* __restrict__ pa
       for (int w = 1; w < T / 64; ++w) a += red[w];
     }
   }
-  if (tid == 0) out[c] = a;
+  return a;
+}
+
+// out[c] = sum over the slices of partial[slice][c]
+template <int T>
+__global__ __launch_bounds__(T) void k_colsum_final(const float* __restrict__ partial, int slices, int C, float* __restrict__ out) {
+  __shared__ float red[T / 64];
+  const float a = ud_colsum_block<T, float>(partial, slices, C, blockIdx.x, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
 inline int ud_colsum_final(const float* partial, int slices, int C, float* out, hipStream_t stream) {
   if (slices > 128) k_colsum_final<256><<<C, 256, 0, stream>>>(partial, slices, C, out);
   else k_colsum_final<64><<<C, 64, 0, stream>>>(partial, slices, C, out);
+  UD_LAUNCH_CHECK();
+  return UD_OK;
+}
+
+// out[g][c] += sum over the slices of partial[g][slice][c], in fp64 and in k_colsum_final's order: `groups` independent column
+// sums in one launch (blockIdx.y), added to what out already holds -- a running total kept on the device (the depth metric of
+// depth_metric.hip).
+template <int T>
+__global__ __launch_bounds__(T) void k_colsum_accum_f64(const double* __restrict__ partial, int slices, int C,
+                                                        double* __restrict__ out) {
+  __shared__ double red[T / 64];
+  const int c = blockIdx.x, g = blockIdx.y;
+  const double a = ud_colsum_block<T, double>(partial + (size_t)g * slices * C, slices, C, c, red);
+  if (threadIdx.x == 0) out[(size_t)g * C + c] += a;
+}
+
+inline int ud_colsum_accum_f64(const double* partial, int groups, int slices, int C, double* out, hipStream_t stream) {
+  if (slices > 128) k_colsum_accum_f64<256><<<dim3(C, groups), 256, 0, stream>>>(partial, slices, C, out);
+  else k_colsum_accum_f64<64><<<dim3(C, groups), 64, 0, stream>>>(partial, slices, C, out);
   UD_LAUNCH_CHECK();
   return UD_OK;
 }

@@ -424,3 +424,79 @@ class NuScenesDetectionEval:
         with open(path, "w") as f:
             json.dump(sub, f)
         return sub
+
+
+def depth_figures(terms):
+    """The twelve sums of ops.depth_metric (float64 [12]) -> the figures; NaN for every ratio of an empty set, n = 0."""
+    t = [float(v) for v in terms]
+    n = t[0]
+    mean = (lambda v: v / n) if n > 0 else (lambda v: float("nan"))
+    root = (lambda v: float(np.sqrt(v / n))) if n > 0 else (lambda v: float("nan"))
+    return {"n": int(round(n)), "abs_rel": mean(t[2]), "sq_rel": mean(t[3]), "rmse": root(t[4]), "rmse_log": root(t[5]),
+            "mae": mean(t[1]), "d1": mean(t[6]), "d2": mean(t[7]), "d3": mean(t[8]), "bin_acc": mean(t[9]),
+            "bin_acc1": mean(t[10]), "nll": mean(t[11])}
+
+
+class DepthMetric:
+    """The camera lift's depth distribution against the LiDAR minimum depth, accumulated on the device.
+
+        m = DepthMetric(d_bound, ncam=6, range_edges=[2, 20, 40, 58], per_camera=True, device=dev)
+        for batch in loader:  m.add_batch(depth_logits, dmin)          # or train.ValidationStep(..., depth_metric=m)
+        figures = m.compute()          # every rank under torch.distributed (one all_reduce of the state)
+
+    ``logits`` [B * ncam, D, fH, fW] are ``LSSFPN(..., is_return_depth="logits")``'s, ``dmin`` is
+    ``LSSFPN.lidar_depth_labels(...)[0]``.  The predicted depth is the softmax's expectation over the bin CENTRES
+    d_lo + (j + 0.5) * d_step.  ``range_edges=None`` is the single bucket [d_lo, d_lo + D * d_step); a labelled pixel outside
+    every bucket of explicit edges is counted nowhere.  ``compute()`` returns n, abs_rel, sq_rel, rmse, rmse_log, mae, d1, d2,
+    d3 (delta < 1.25^k), bin_acc, bin_acc1 (arg-max bin equal to / within one of the label bin) and nll (-ln p of the label
+    bin) over everything counted, formed from the summed terms; with explicit edges ``"ranges"``: a list of the same figures
+    per bucket (plus ``lo``, ``hi``), with per_camera ``"cameras"``: a list per camera."""
+
+    def __init__(self, d_bound, ncam=1, range_edges=None, per_camera=False, device=None):
+        from .ops import depth_metric as op
+        self.d_bound = [float(v) for v in d_bound]
+        lo, step, D = op.depth_bins(self.d_bound)
+        self.explicit_ranges = range_edges is not None
+        self.range_edges = [float(v) for v in range_edges] if self.explicit_ranges else [lo, lo + D * step]
+        R = len(self.range_edges) - 1
+        if not 1 <= R <= op.MAX_RANGES:
+            raise ValueError(f"1 .. {op.MAX_RANGES} range buckets supported, got {R}")
+        if any(not b > a for a, b in zip(self.range_edges, self.range_edges[1:])):
+            raise ValueError(f"range_edges must ascend, got {self.range_edges}")
+        self.ncam = int(ncam)
+        if self.ncam < 1:
+            raise ValueError(f"ncam must be at least 1, got {ncam}")
+        self.per_camera = bool(per_camera)
+        self.groups = self.ncam if self.per_camera else 1
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.state = torch.zeros((self.groups, R, len(op.TERMS)), dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        self.state.zero_()
+
+    def add_batch(self, logits, dmin):
+        """logits [B * ncam, D, fH, fW], dmin f32[B, ncam, fH, fW] (or [B * ncam, fH, fW]); nothing is read back."""
+        from .ops import depth_metric as op
+        if logits.shape[0] % self.ncam:
+            raise ValueError(f"{logits.shape[0]} images are not a multiple of ncam = {self.ncam}")
+        op.depth_metric_accumulate(logits, dmin, self.state, self.d_bound, self.range_edges, self.groups)
+
+    def _reduced_state(self):
+        """The state summed over the ranks, on the host: the single read."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            host_backend = dist.get_backend() == "gloo"            # gloo moves host buffers: stage through the host
+            buf = self.state.to("cpu", copy=True) if host_backend else self.state.clone()   # the state itself stays local
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+            return buf.cpu()
+        return self.state.cpu()
+
+    def compute(self):
+        s = self._reduced_state().numpy()                          # [groups, ranges, 12]
+        out = depth_figures(s.sum((0, 1)))
+        if self.explicit_ranges:
+            out["ranges"] = [dict(depth_figures(s[:, r].sum(0)), lo=self.range_edges[r], hi=self.range_edges[r + 1])
+                             for r in range(s.shape[1])]
+        if self.per_camera:
+            out["cameras"] = [depth_figures(s[g].sum(0)) for g in range(s.shape[0])]
+        return out

@@ -113,17 +113,20 @@ class BEVFusionCenterHead(nn.Module):
 
     def forward(self, lidar_points=None, cameras_imgs=None, metas=None, gt_boxes=None,
                 return_feature=False, targets=None, loss_norm=None, lidar_prepared=None, depth_label=None,
-                depth_weight=None, **_):
+                depth_weight=None, return_depth_logits=False, **_):
         """targets / loss_norm: optional precomputed FCOS targets and globally reduced loss
         normalisers (train.py computes them up front so the network pass holds no collective);
         lidar_prepared: LidarEncoder.prepare(lidar_points), when the caller ran it ahead of time;
         depth_label / depth_weight: LiDAR depth-bin labels i32[B, ncam, fH, fW] (LSSFPN.lidar_depth_labels) and the weight
         of the depth loss (BEVDepth: 3.0).  With both, in training, on a model with a camera encoder,
-        depth_weight * ops.depth_sup.depth_loss joins ret['loss'] and tb['loss_depth'] holds the unweighted term."""
+        depth_weight * ops.depth_sup.depth_loss joins ret['loss'] and tb['loss_depth'] holds the unweighted term.
+        return_depth_logits: in eval mode, on a model with a camera encoder, the returned dict also holds 'depth_logits',
+        the key frame's depth logits [B * ncam, D, fH, fW] of this very forward (evaluation.DepthMetric reads them)."""
         depth_sup = (depth_label is not None and depth_weight is not None and self.training and not return_feature
                      and self.with_camera_encoder)
+        eval_logits = return_depth_logits and not self.training and not return_feature and self.with_camera_encoder
         depth_logits = None
-        if depth_sup:
+        if depth_sup or eval_logits:
             bev, depth_logits = self.extract_bev(lidar_points, cameras_imgs, metas, lidar_prepared, return_depth_logits=True)
         else:
             bev = self.extract_bev(lidar_points, cameras_imgs, metas, lidar_prepared)
@@ -144,4 +147,6 @@ class BEVFusionCenterHead(nn.Module):
                 loss = loss + depth_weight * loss_depth
                 tb["loss_depth"] = loss_depth.detach()
             return {"loss": loss}, tb, bev_out, trunk_out, ret["multi_head_features"], {}
+        if eval_logits:
+            ret["depth_logits"] = depth_logits
         return ret

@@ -424,15 +424,35 @@ class ValidationStep(nn.Module):
     the predictions go to a NuScenesDetectionEval on the device (labels start at 1 there; the evaluator subtracts 1).
 
     ``weights``: a zero-argument callable returning a context manager inside which the forward runs, e.g.
-    ``trainer.ema_weights`` to validate with the averaged weights; ``None`` runs the model as it is."""
+    ``trainer.ema_weights`` to validate with the averaged weights; ``None`` runs the model as it is.
 
-    def __init__(self, model, evaluator, weights=None):
+    ``depth_metric``: an ``evaluation.DepthMetric``; the eval forward's own depth logits (inside ``weights()``, so the
+    averaged weights are the ones measured) and the batch's LiDAR minimum depth are added to it, on the device.  Needs a
+    model with a camera encoder and a batch with 'points' and 'mats_dict'.  ``None``: the step is unchanged."""
+
+    def __init__(self, model, evaluator, weights=None, depth_metric=None):
         super().__init__()
         self.model = model
         self.evaluator = evaluator
         self.weights = weights
+        self.depth_metric = depth_metric
+
+    def _check_depth_inputs(self, batch):
+        if self.model.camera_encoder is None:
+            raise ValueError("depth_metric is set, but the model has no camera encoder whose depth it could measure")
+        if batch.get("points") is None or batch.get("mats_dict") is None:
+            raise ValueError("depth_metric is set, but the batch carries no LiDAR 'points' (or no 'mats_dict') to build the "
+                             "depth labels from: a camera-only batch has no depth to measure against")
+
+    def _forward_with_depth_metric(self, batch, points):
+        out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None, return_depth_logits=True)
+        dmin = self.model.camera_encoder.backbone.lidar_depth_labels(batch["points"], batch["mats_dict"])[0]
+        self.depth_metric.add_batch(out.pop("depth_logits"), dmin)
+        return out
 
     def forward(self, batch, sample_ids, lidar_to_global):
+        if self.depth_metric is not None:
+            self._check_depth_inputs(batch)
         points = batch.get("points")
         if points is not None and not isinstance(points, (list, tuple)):
             points = [p for p in points]
@@ -441,7 +461,10 @@ class ValidationStep(nn.Module):
         try:
             weights = contextlib.nullcontext() if self.weights is None else self.weights()
             with weights, torch.no_grad():
-                out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None)
+                if self.depth_metric is not None:
+                    out = self._forward_with_depth_metric(batch, points)
+                else:
+                    out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None)
         finally:
             self.model.train(was_training)
         self.evaluator.add_batch(sample_ids, out["pred_dicts"], lidar_to_global)

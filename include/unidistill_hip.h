@@ -1167,6 +1167,32 @@ int ud_lidar_paste_compact(const float* pts, int64_t rows, int D, const int64_t*
                            const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact, float* out,
                            int64_t out_rows, void* workspace, size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- Depth metric of the camera student's lift (csrc/depth_metric.hip) ------------------------------
+ * The monocular-depth figures of the lift against the LiDAR minimum depth, accumulated on the device.
+ *   logits f32[BN, D, fH, fW] through element strides (sn, sc, sh, sw), D <= 256: NCHW or the channels-last slice
+ *   depth_feature[:, :D], no copy.  dmin f32[BN, fH, fW] as ud_depth_labels writes it (+inf = no LiDAR return).
+ *   A pixel is labelled when dmin is finite and b = floor(((double)dmin - d_lo) / d_step) lies in [0, D): ud_depth_labels'
+ *   own expression, so the pixel set is its label >= 0 bit for bit.  Per labelled pixel, in fp32 (the two sums over D are
+ *   carried in fp64 and rounded to fp32 once): p = softmax over D with the maximum subtracted;  dhat = sum_j p_j * (d_lo + (j + 0.5) * d_step), the expectation over the bin CENTRES (label
+ *   bin j covers [d_lo + j * d_step, d_lo + (j + 1) * d_step));  ahat = the arg-max bin, the lowest index on a tie.
+ *   With d = dmin and e = dhat - d, in fp64 from the fp32 dhat, the T = 12 terms in this order:
+ *     0 count   1 sum |e|   2 sum |e| / d   3 sum e^2 / d   4 sum e^2   5 sum (ln dhat - ln d)^2
+ *     6..8 #[max(dhat / d, d / dhat) < 1.25^k], k = 1, 2, 3   9 #[ahat == b]   10 #[|ahat - b| <= 1]
+ *     11 sum -ln max(p_b, 1e-44)
+ *   Group g = n mod ncam_groups (ncam for a per-camera breakdown of [B * ncam] images, 1 for none); range bucket r = the
+ *   first r with range_edges[r] <= d < range_edges[r + 1] (range_edges: n_ranges + 1 strictly ascending doubles on the
+ *   HOST, read before the call returns; 1 <= n_ranges <= 8); a labelled pixel outside every bucket is counted in none.
+ *   state f64[ncam_groups, n_ranges, 12] += this call (the caller zeroes it once).  Every 64 consecutive pixels of an
+ *   image make one fp64 partial row in the workspace, a second launch adds the rows in a fixed order: no floating-point
+ *   atomics, bitwise reproducible, the partition a function of the shape alone.  Two launches, no host
+ *   synchronisation, no allocation.  UD_ERR_INVALID_ARG with nothing launched: D outside 1..256, n_ranges outside
+ *   1..8, edges that do not ascend, ncam_groups < 1, BN % ncam_groups != 0, a negative size.  BN == 0 or fH * fW == 0: UD_OK, nothing done. */
+size_t ud_depth_metric_workspace_bytes(int BN, int fH, int fW);
+int ud_depth_metric_accumulate(const float* logits, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const float* dmin,
+                               int BN, int D, int fH, int fW, int ncam_groups, double d_lo, double d_step,
+                               const double* range_edges, int n_ranges, double* state, void* workspace,
+                               size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
