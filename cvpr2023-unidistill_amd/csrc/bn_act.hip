@@ -281,6 +281,83 @@ __global__ __launch_bounds__(256) void k_bn_bwd_dx(const T* __restrict__ x, cons
   }
 }
 
+// ---- frozen statistics (eval-mode BatchNorm with a gradient wanted: frozen_bn / norm_eval fine-tuning, base.py:61-67).  The
+// statistics are constants, so dx = scale * dr depends on no reduction: one pass writes dx (+ dres); when gamma / beta train, the
+// same pass also leaves the per-slice sums of k_bn_bwd_reduce for the shared finalize (two launches instead of three).
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_frozen_dx(const T* __restrict__ x, const T* __restrict__ y,
+                                                          const T* __restrict__ dy,
+                                                          const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, T* __restrict__ dx,
+                                                          T* __restrict__ dres, long long P, int C,
+                                                          int CH, int relu, long long dy_ld) {
+  const int chunk = blockIdx.y * CH + threadIdx.x % CH, lanes = 256 / CH, pl = threadIdx.x / CH;
+  if (chunk * 8 >= C) return;
+  float s[8], t[8];
+  load8(scale + chunk * 8, s);
+  load8(shift + chunk * 8, t);
+  const bool mask_from_x = relu && !y;               // without a ReLU, or with the saved output as the mask source, x is not read
+  for (long long p = (long long)blockIdx.x * lanes + pl; p < P; p += (long long)gridDim.x * lanes) {
+    const size_t off = (size_t)p * C + chunk * 8;
+    float xv[8], dyv[8], dr[8], o[8], yv[8];
+    if (mask_from_x) ld8(x + off, xv);
+    ld8(dy + (size_t)p * dy_ld + chunk * 8, dyv);
+    if (y) ld8(y + off, yv);
+    masked_grad(xv, yv, y != nullptr, dyv, s, t, relu, dr);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = s[e] * dr[e];
+    st8(dx + off, o);
+    if (dres) st8(dres + off, dr);
+  }
+}
+
+// grid (slices, C/GW), k_bn_bwd_reduce's mapping and summation order: dx (+ dres) written on the way,
+// partial[slice][C][2] = sum dr, sum dr * (x - mean)
+template <int GW, typename T>
+__global__ __launch_bounds__(256) void k_bn_bwd_frozen_sums(const T* __restrict__ x, const T* __restrict__ y,
+                                                            const T* __restrict__ dy,
+                                                            const float* __restrict__ scale,
+                                                            const float* __restrict__ shift,
+                                                            const float* __restrict__ mean, T* __restrict__ dx,
+                                                            T* __restrict__ dres, long long P, int C, int relu,
+                                                            float* __restrict__ partial, long long dy_ld) {
+  using M = GroupMap<GW>;
+  __shared__ float red[M::kLanes][GW + 1][2];
+  const int cg = blockIdx.y, tid = threadIdx.x, chunk = tid % M::kChunks, pl = tid / M::kChunks;
+  const int c0 = cg * GW + chunk * 8;
+  float s[8], t[8], mu[8], s1[8], s2[8];
+  load8(scale + c0, s);
+  load8(shift + c0, t);
+  load8(mean + c0, mu);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
+  for (long long p = (long long)blockIdx.x * M::kLanes + pl; p < P; p += (long long)gridDim.x * M::kLanes) {
+    const size_t off = (size_t)p * C + c0;
+    float xv[8], dyv[8], dr[8], o[8], yv[8];
+    ld8(x + off, xv);
+    ld8(dy + (size_t)p * dy_ld + c0, dyv);
+    if (y) ld8(y + off, yv);
+    masked_grad(xv, yv, y != nullptr, dyv, s, t, relu, dr);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      o[e] = s[e] * dr[e];
+      s1[e] += dr[e];
+      s2[e] += dr[e] * (xv[e] - mu[e]);
+    }
+    st8(dx + off, o);
+    if (dres) st8(dres + off, dr);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { red[pl][chunk * 8 + e][0] = s1[e]; red[pl][chunk * 8 + e][1] = s2[e]; }
+  __syncthreads();
+  if (tid < 2 * GW) {
+    const int c = tid >> 1, w = tid & 1;
+    float a = 0.f;
+    for (int i = 0; i < M::kLanes; ++i) a += red[i][c][w];
+    partial[((size_t)blockIdx.x * C + cg * GW + c) * 2 + w] = a;
+  }
+}
+
 
 // ---- column sums: out[c] = sum_p x[p * ld + c] -- the bias gradient of a convolution (sum of dy over batch and pixels:
 // center_head.py:64,339,353 bias=True; the depth net's 1x1) as two HBM-rate passes in a fixed order.  (ATen's reduce_kernel
@@ -451,6 +528,43 @@ int bn_bwd_impl(const T* x, const T* y, const T* dy, const float* scale, const f
   return UD_OK;
 }
 
+// dgamma / dbeta both null: the affine parameters take no gradient -- one launch, no workspace, mean / invstd unused
+template <typename T>
+int bn_bwd_frozen_impl(const T* x, const T* y, const T* dy, const float* scale, const float* shift, const float* mean,
+                       const float* invstd, T* dx, T* dresidual, float* dgamma, float* dbeta, long long P, int C, int relu,
+                       long long dy_ld, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const bool sums = dgamma != nullptr;
+  if (!x || !dy || !scale || !shift || !dx || (dgamma == nullptr) != (dbeta == nullptr) || (sums && (!mean || !invstd)) ||
+      P <= 0 || C <= 0 || dy_ld < C)
+    return UD_ERR_INVALID_ARG;
+  if (C % 16 || dy_ld % 8 || ((size_t)dy & 15)) return UD_ERR_UNSUPPORTED;
+  if (!sums) {
+    int CH;
+    dim3 grid;
+    stream_grid(P, C, &CH, &grid);
+    UdProfScope prof("bn_act.k_bwd_frozen_dx", stream);
+    k_bn_bwd_frozen_dx<T><<<grid, 256, 0, stream>>>(x, y, dy, scale, shift, dx, dresidual, P, C, CH, relu, dy_ld);
+    UD_LAUNCH_CHECK();
+    return UD_OK;
+  }
+  UdArena ar(workspace, workspace_bytes);
+  BnWs w;
+  carve(ar, C, &w);
+  if (!ar.ok()) return UD_ERR_WORKSPACE;
+  UdProfScope prof("bn_act.k_bwd_frozen_sums", stream);
+  const int slices = slices_for(P, C), gw = group_width(C);
+  if (gw == 64)
+    k_bn_bwd_frozen_sums<64, T><<<dim3(slices, C / 64), 256, 0, stream>>>(x, y, dy, scale, shift, mean, dx, dresidual, P, C, relu, w.partial, dy_ld);
+  else if (gw == 32)
+    k_bn_bwd_frozen_sums<32, T><<<dim3(slices, C / 32), 256, 0, stream>>>(x, y, dy, scale, shift, mean, dx, dresidual, P, C, relu, w.partial, dy_ld);
+  else
+    k_bn_bwd_frozen_sums<16, T><<<dim3(slices, C / 16), 256, 0, stream>>>(x, y, dy, scale, shift, mean, dx, dresidual, P, C, relu, w.partial, dy_ld);
+  UD_LAUNCH_CHECK();
+  // the training-mode finalize: dbeta = sum dr, dgamma = invstd * sum dr (x - mean); its k0 / k2 (the batch-statistics terms of dx)
+  // land in the workspace and are not read
+  return ud_bn_bwd_final(w.partial, slices, C, P, scale, mean, invstd, dgamma, dbeta, w.k0, w.k2, stream);
+}
+
 template <typename T>
 int colsum_impl(const T* x, long long P, int C, long long ld, float* out, void* workspace, size_t workspace_bytes,
                 hipStream_t stream) {
@@ -581,6 +695,22 @@ int ud_bn_act_bwd_ld_f32(const float* x, const float* y, const float* dy, long l
                          size_t workspace_bytes, ud_stream_t stream) {
   return bn_bwd_impl<float>(x, y, dy, scale, shift, mean, invstd, dx, dresidual, dgamma, dbeta, P, C, relu, dy_ld,
                             workspace, workspace_bytes, (hipStream_t)stream);
+}
+// Backward through FROZEN statistics (an eval-mode BatchNorm inside a training graph): dx = scale * dr, no batch terms.
+int ud_bn_act_bwd_frozen_ld(const void* x, const void* y, const void* dy, long long dy_ld, const float* scale,
+                            const float* shift, const float* mean, const float* invstd, void* dx, void* dresidual,
+                            float* dgamma, float* dbeta, long long P, int C, int relu, void* workspace,
+                            size_t workspace_bytes, ud_stream_t stream) {
+  return bn_bwd_frozen_impl<bf16_t>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, scale, shift, mean, invstd,
+                                    (bf16_t*)dx, (bf16_t*)dresidual, dgamma, dbeta, P, C, relu, dy_ld, workspace,
+                                    workspace_bytes, (hipStream_t)stream);
+}
+int ud_bn_act_bwd_frozen_ld_f32(const float* x, const float* y, const float* dy, long long dy_ld, const float* scale,
+                                const float* shift, const float* mean, const float* invstd, float* dx, float* dresidual,
+                                float* dgamma, float* dbeta, long long P, int C, int relu, void* workspace,
+                                size_t workspace_bytes, ud_stream_t stream) {
+  return bn_bwd_frozen_impl<float>(x, y, dy, scale, shift, mean, invstd, dx, dresidual, dgamma, dbeta, P, C, relu, dy_ld,
+                                   workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t ud_colsum_workspace_bytes(int C) { return C > 0 ? ud_align_up((size_t)kMaxSlices * C * sizeof(float)) : 0; }

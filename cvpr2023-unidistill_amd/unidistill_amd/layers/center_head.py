@@ -481,12 +481,13 @@ class PackedSepHeads(nn.Module):
                                     self.bn_running_mean, self.bn_running_var, self.training,
                                     self.bn_momentum, self.bn_eps, G, self.kmax)
             return self._split(z)
-        if Conv2d.hip_enabled and Conv2d.hip_fp32 and not torch.is_autocast_enabled("cuda") and not frozen_bn_grad \
-                and head_tail_f32.supported(y, self.head_conv, self.kmax, self.k) and (self.training or not torch.is_grad_enabled()):
+        if Conv2d.hip_enabled and Conv2d.hip_fp32 and not torch.is_autocast_enabled("cuda") \
+                and head_tail_f32.supported(y, self.head_conv, self.kmax, self.k) \
+                and (self.training or not torch.is_grad_enabled() or frozen_bn_grad):
             # fp32 mode on the GPU: BN + ReLU as one streaming pass, then the 42 second convs as ONE grouped fp32
             # kernel (the block-diagonal dense conv below costs 42x the FLOPs: 19 ms per fwd+bwd at B = 4)
             partial = getattr(y, "_ud_bn_partial", None) if self.training else None
-            if self.fused_bn_tail_f32:
+            if self.fused_bn_tail_f32 and not frozen_bn_grad:       # (the fused tail's backward is training-mode only)
                 # ... with BatchNorm + ReLU applied inside the tail kernels as they load y: the normalised hidden tensor never exists
                 return self._split(head_tail_f32.bn_relu_group_tail(
                     y, self.bn_weight, self.bn_bias, self.bn_running_mean, self.bn_running_var, self.training,

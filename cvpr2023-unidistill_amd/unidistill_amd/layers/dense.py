@@ -184,15 +184,16 @@ _HIP_BN = os.environ.get("UD_HIP_BN", "1") != "0"      # A/B switch for the stre
 
 
 def batchnorm_act(bn, x, residual=None, relu=True, out=None):
-    """relu(bn(x) (+ residual)): the streaming HIP kernels in bf16 channels-last mode (training-mode
-    statistics with autograd, or eval-mode without), the PyTorch ops otherwise.  out: a channel slice of a concatenation
-    buffer (ops/bn_act.cat_buffer) the HIP path writes in place; the other paths ignore it (the caller checks the result)."""
-    frozen_grad = (not bn.training) and wants_grad(x, residual, bn)
-    if Conv2d.hip_enabled and _HIP_BN and isinstance(bn, (nn.BatchNorm2d, nn.BatchNorm1d)) \
-            and not frozen_grad and hipbn.supported(x, bn):
+    """relu(bn(x) (+ residual)): the streaming HIP kernels on channels-last maps / voxel rows (training-mode statistics, or
+    eval-mode ones -- with autograd too: a frozen BatchNorm inside a training graph, ud_bn_act_bwd_frozen_ld*), the PyTorch ops
+    otherwise.  out: a channel slice of a concatenation buffer (ops/bn_act.cat_buffer) the HIP path writes in place; the other
+    paths ignore it (the caller checks the result)."""
+    if Conv2d.hip_enabled and _HIP_BN and isinstance(bn, (nn.BatchNorm2d, nn.BatchNorm1d)) and hipbn.supported(x, bn):
         if out is not None and not (x.dim() == 4 and out.shape == x.shape and out.dtype == x.dtype):
             out = None
         return hipbn.bn_act(bn, x, residual, relu, out)
+    # a tensor the kernels do not take (layout, channel count): as before, a frozen BatchNorm with a gradient wanted is let through
+    frozen_grad = (not bn.training) and wants_grad(x, residual, bn)
     if Conv2d.hip_enabled and _HIP_BN and not frozen_grad:
         _lib.library_fallthrough("layers.dense.batchnorm_act", x, training=bn.training)
     y = bn(x)

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from ..ops import spconv as sp
+from .base import BaseEncoder
 from ..ops.voxelize import MeanVFE, Voxelization, voxelize_confirm, voxelize_deferred, voxelize_dirty
 
 
@@ -127,16 +128,17 @@ class HeightCompression(nn.Module):
         return encoded_spconv_tensor.bev(), encoded_spconv_tensor_stride
 
 
-class LidarEncoder(nn.Module):
+class LidarEncoder(BaseEncoder):
     """points -> voxelize -> MeanVFE -> VoxelResBackBone8x -> HeightCompression -> [B,256,180,180].
 
     cfg needs: voxel_size, point_cloud_range, grid_size, max_num_points, max_voxels,
     src_num_point_features, use_num_point_features, map_to_bev_num_features
     (base_nuscenes_cfg.py:107-116).  The voxelizer runs fused with MeanVFE (no [M,10,5] tensor).
+    frozen_encoder / frozen_bn: the reference's BaseEncoder switches (layers/base.py), applied by train().
     """
 
-    def __init__(self, cfg, fused_mean=True):
-        super().__init__()
+    def __init__(self, cfg, fused_mean=True, frozen_encoder=False, frozen_bn=False):
+        super().__init__(frozen_encoder, frozen_bn)
         self.cfg = cfg
         g = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
         self.voxelizer = Voxelization(voxel_size=g("voxel_size"), point_cloud_range=g("point_cloud_range"),

@@ -9,6 +9,7 @@ Mirrors, with state_dict-compatible sub-module names,
 import torch
 from torch import nn
 
+from .layers.base import BaseEncoder
 from .layers.bev import BevEncoder, FusionEncoder
 from .layers.center_head import CenterHeadIouAware, FCOSAssigner
 from .layers.gen_proposals import IouAwareGenProposals
@@ -17,9 +18,12 @@ from .layers.lss_fpn import LSSFPN
 from .ops.distill import feature_tap
 
 
-class CameraEncoder(nn.Module):
-    def __init__(self, camera_encoder_cfg, **kw):
-        super().__init__()
+class CameraEncoder(BaseEncoder):
+    """frozen_encoder / frozen_bn: the reference's BaseEncoder switches (layers/base.py), applied by train(); the image
+    backbone's own frozen_stages / norm_eval (layers/image.ResNet.train) compose with them."""
+
+    def __init__(self, camera_encoder_cfg, frozen_encoder=False, frozen_bn=False, **kw):
+        super().__init__(frozen_encoder, frozen_bn)
         self.backbone = LSSFPN(**camera_encoder_cfg, **kw)
 
     def forward(self, imgs, mats_dict, is_return_depth=False):
@@ -79,13 +83,18 @@ class BEVFusionCenterHead(nn.Module):
                          roi_scores, roi_labels (layers/gen_proposals.py, rotated NMS on the HIP library)
     """
 
-    def __init__(self, model_cfg, camera_kwargs=None):
+    def __init__(self, model_cfg, camera_kwargs=None, lidar_kwargs=None):
+        """camera_kwargs / lidar_kwargs (and model_cfg["camera_encoder_kwargs"] / ["lidar_encoder_kwargs"], which they
+        override): constructor arguments of the two encoders beyond their cfg, e.g. frozen_bn=True, frozen_encoder=True."""
         super().__init__()
         self.cfg = model_cfg
         self.class_names = model_cfg["class_names"]
         self.num_class = len(self.class_names)
-        self.lidar_encoder = LidarEncoder(model_cfg["lidar_encoder"]) if model_cfg.get("lidar_encoder") else None
-        self.camera_encoder = (CameraEncoder(model_cfg["camera_encoder"], **(camera_kwargs or {}))
+        lidar_kwargs = {**(model_cfg.get("lidar_encoder_kwargs") or {}), **(lidar_kwargs or {})}
+        camera_kwargs = {**(model_cfg.get("camera_encoder_kwargs") or {}), **(camera_kwargs or {})}
+        self.lidar_encoder = (LidarEncoder(model_cfg["lidar_encoder"], **lidar_kwargs)
+                              if model_cfg.get("lidar_encoder") else None)
+        self.camera_encoder = (CameraEncoder(model_cfg["camera_encoder"], **camera_kwargs)
                                if model_cfg.get("camera_encoder") else None)
         both = self.lidar_encoder is not None and self.camera_encoder is not None
         self.fusion_encoder = FusionEncoder(use_elementwise=False) if both else None

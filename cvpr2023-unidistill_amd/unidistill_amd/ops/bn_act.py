@@ -173,8 +173,6 @@ class _BnActFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, y, vec = ctx.saved_tensors
         training, relu, has_res = ctx.cfg
-        if not training:
-            raise NotImplementedError("fused BatchNorm backward covers training-mode statistics only")
         if y is not None and y.stride() != x.stride():
             y = _like(y, x)               # written into a channel slice (out=): the backward kernels read the mask source at p * C + c
         C = x.shape[1]
@@ -186,15 +184,33 @@ class _BnActFn(torch.autograd.Function):
         dres = torch.empty_like(x) if (has_res and ctx.needs_input_grad[3]) else None
         if dres is not None and not relu:
             dres = None                                   # no mask: the residual gradient is dy itself
-        dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
-        ws = _workspace(x.device, C)
-        v0, row, g0 = vec.data_ptr(), 4 * C, dgb.data_ptr()
-        k_bwd = _lib.ud.ud_bn_act_bwd_ld_f32 if x.dtype == torch.float32 else _lib.ud.ud_bn_act_bwd_ld
-        k_bwd(x.data_ptr(), y, dy.data_ptr(), ld, v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row, dx.data_ptr(), dres, g0, g0 + row,
-              P, C, 1 if relu else 0, ws.data_ptr(), ws.numel(), _lib.stream_of(x))
+        v0, row = vec.data_ptr(), 4 * C
+        if training:
+            dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+            ws = _workspace(x.device, C)
+            g0 = dgb.data_ptr()
+            k_bwd = _lib.ud.ud_bn_act_bwd_ld_f32 if x.dtype == torch.float32 else _lib.ud.ud_bn_act_bwd_ld
+            k_bwd(x.data_ptr(), y, dy.data_ptr(), ld, v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row, dx.data_ptr(), dres, g0,
+                  g0 + row, P, C, 1 if relu else 0, ws.data_ptr(), ws.numel(), _lib.stream_of(x))
+            dgamma, dbeta = dgb[0], dgb[1]
+        else:
+            # frozen statistics (eval mode inside a training graph): dx = scale * dr needs no reduction; the affine sums are made
+            # by the same pass, and only when gamma or beta takes a gradient (else ONE launch)
+            k_bwd = _lib.ud.ud_bn_act_bwd_frozen_ld_f32 if x.dtype == torch.float32 else _lib.ud.ud_bn_act_bwd_frozen_ld
+            dgamma = dbeta = dgb = ws = None
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+                ws = _workspace(x.device, C)
+            g0 = None if dgb is None else dgb.data_ptr()
+            k_bwd(x.data_ptr(), y, dy.data_ptr(), ld, v0 + 3 * row, v0 + 4 * row, v0, v0 + 2 * row, dx.data_ptr(), dres, g0,
+                  None if dgb is None else g0 + row, P, C, 1 if relu else 0, ws, 0 if ws is None else ws.numel(),
+                  _lib.stream_of(x))
+            if dgb is not None:
+                dgamma = dgb[0] if ctx.needs_input_grad[1] else None
+                dbeta = dgb[1] if ctx.needs_input_grad[2] else None
         if has_res and ctx.needs_input_grad[3] and dres is None:
             dres = dy
-        return dx, dgb[0], dgb[1], dres, None, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None
 
 
 class _CatSlices(torch.autograd.Function):

@@ -21,9 +21,18 @@ from .models import BEVFusionCenterHead
 from .ops import distill as D, wgrad_stream
 
 
-def build_model(modality, iou_mode=None, **kw):
-    """modality: 'camera' | 'lidar' | 'fusion' -> BEVFusionCenterHead."""
+def build_model(modality, iou_mode=None, frozen_bn=False, frozen_encoder=False, **kw):
+    """modality: 'camera' | 'lidar' | 'fusion' -> BEVFusionCenterHead.
+    frozen_bn / frozen_encoder: the reference's BaseEncoder switches (layers/base.py) -- True for every encoder of the model, or
+    the encoders they apply to ('lidar', 'camera', or a collection of the two: the frozen LiDAR half of a fusion student)."""
     cfg = C.model_cfg(lidar=modality in ("lidar", "fusion"), camera=modality in ("camera", "fusion"), iou_mode=iou_mode)
+    for flag, val in (("frozen_bn", frozen_bn), ("frozen_encoder", frozen_encoder)):
+        which = ("lidar", "camera") if val is True else ((val,) if isinstance(val, str) else tuple(val or ()))
+        if set(which) - {"lidar", "camera"}:
+            raise ValueError(f"{flag}: expected True / False, 'lidar', 'camera' or a collection of the two, got {val!r}")
+        for enc in which:
+            if cfg.get(f"{enc}_encoder"):
+                cfg.setdefault(f"{enc}_encoder_kwargs", {})[flag] = True
     return BEVFusionCenterHead(cfg, **kw)
 
 

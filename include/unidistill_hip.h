@@ -865,6 +865,23 @@ int ud_bn_act_bwd_ld_f32(const float* x, const float* y, const float* dy, long l
                          const float* shift, const float* mean, const float* invstd, float* dx, float* dresidual,
                          float* dgamma, float* dbeta, long long P, int C, int relu, void* workspace,
                          size_t workspace_bytes, ud_stream_t stream);
+/* Backward through FROZEN statistics: an eval-mode BatchNorm inside a training graph (the reference's frozen_bn /
+ * frozen_encoder, models/multisensor_fusion/base.py:50-67; mmdet's norm_eval).  scale / shift / mean / invstd are the vectors
+ * folded from the running buffers; the shape rules are those of ud_bn_act_bwd_ld* (C % 16 == 0, dy a channel slice with row
+ * stride dy_ld, y the saved output when a residual took part).
+ *   dx = scale * dr, dresidual (optional) = dr, dr = dy under the ReLU mask of the training-mode kernels.
+ *   dgamma, dbeta: both given -> dbeta = sum dr, dgamma = invstd * sum dr (x - mean): the pass that writes dx leaves per-slice
+ *     partial sums, a fixed-order kernel adds them (two launches, no atomics, bitwise reproducible; workspace of
+ *     ud_bn_act_workspace_bytes(C)).  Both NULL (frozen affine parameters) -> ONE launch, no reduction; mean, invstd and the
+ *     workspace are not read and may be NULL / 0. */
+int ud_bn_act_bwd_frozen_ld(const void* x, const void* y, const void* dy, long long dy_ld, const float* scale,
+                            const float* shift, const float* mean, const float* invstd, void* dx, void* dresidual,
+                            float* dgamma, float* dbeta, long long P, int C, int relu, void* workspace,
+                            size_t workspace_bytes, ud_stream_t stream);
+int ud_bn_act_bwd_frozen_ld_f32(const float* x, const float* y, const float* dy, long long dy_ld, const float* scale,
+                                const float* shift, const float* mean, const float* invstd, float* dx, float* dresidual,
+                                float* dgamma, float* dbeta, long long P, int C, int relu, void* workspace,
+                                size_t workspace_bytes, ud_stream_t stream);
 
 /* ---- Proposal layer: rotated-BEV IoU + greedy NMS -----------------------------------------------------
  * Replaces `iou3d_nms_cuda.nms_gpu(boxes, keep, thresh)` (reference layers/head/det3d/generate_proposals/
