@@ -27,6 +27,7 @@
 #include "ud_common.h"
 #include "ud_prof.h"
 #include "points_xform.h"
+#include "box_inside.h"        // RmBox, in_rm_box: the inside test, shared with gt_database.hip
 
 namespace {
 
@@ -38,11 +39,6 @@ constexpr int kMaxSeg = UD_LIDAR_MAX_SEGMENTS;
 // seg_par[s]: see UD_LIDAR_SEG_PAR in unidistill_hip.h; smp_par[b]: UD_LIDAR_SMP_PAR.
 constexpr int kSegMat = 0, kSegLast = 16, kSegXform = 17;
 constexpr int kSmpBda = 0, kSmpRange = 16, kSmpHasBda = 22, kSmpHasRange = 23;
-
-// An accepted removal box as the inside test reads it.
-struct RmBox {
-  float cx, cy, cz, hx, hy, hz, sn, cs;
-};
 
 // The paste arguments of a launch (all NULL / 0 for a segment table alone).
 struct PasteArgs {
@@ -78,13 +74,6 @@ __device__ __forceinline__ int stage_rm_boxes(const PasteArgs& pa, int b, RmBox*
   }
   __syncthreads();
   return *s_nrm;
-}
-
-__device__ __forceinline__ bool in_rm_box(const RmBox& r, const float xyz[3]) {
-  const float sx = xyz[0] - r.cx, sy = xyz[1] - r.cy;
-  if (!(fabsf(xyz[2] - r.cz) <= r.hz)) return false;
-  const float lx = sx * r.cs + sy * r.sn, ly = -sx * r.sn + sy * r.cs;
-  return fabsf(lx) < r.hx && fabsf(ly) < r.hy;
 }
 
 struct SampleRows {

@@ -7,6 +7,10 @@ indices (host, a handful of integers) and records them in data_dict["lidar_aug"]
 ud_lidar_paste_compact) reads the accepted objects' clouds straight out of the device-resident ``ObjectDatabase``,
 drops the scene's points inside their boxes and goes on with BDA, range filter, compaction and padding as before.
 Images are not edited (the reference's MultiModalGTSampling is a no-op too): a camera branch sees the unpasted scene.
+
+The database itself is built here too: ``ObjectDatabaseBuilder`` is OpenPCDet's
+create_groundtruth_database on the device -- ``points_in_boxes`` (ud_points_in_boxes) over whole scenes, then a stable
+per-object compaction (ud_gt_db_count / ud_gt_db_extract) -- and ``ObjectDatabase.save`` / ``load`` keep it in one .npz.
 """
 import numpy as np
 import torch
@@ -126,6 +130,225 @@ class ObjectDatabase:
         offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])])
         return cls.from_arrays(np.concatenate(clouds), offsets, np.stack(boxes), ids, class_names, device,
                                filter_by_min_points_cfg, npts, name)
+
+    def save(self, path):
+        """The whole database as one .npz at ``path`` (written as given, no suffix added): points, offsets, boxes,
+        class_ids, class_names.  ``load`` gives it back bit for bit."""
+        with open(path, "wb") as f:
+            np.savez(f, points=self.points.cpu().numpy(), offsets=self.offsets, boxes=self.boxes,
+                     class_ids=self.class_ids, class_names=np.array(self.class_names, dtype=np.str_))
+
+    @classmethod
+    def load(cls, path, device="cuda", name=None):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(z["points"], z["offsets"], z["boxes"], z["class_ids"], [str(c) for c in z["class_names"]], device,
+                       name)
+
+
+# ---- building the database on the device (DESIGN §2.19) --------------------------------------------------------------
+def _scene_offsets(points, seg, boxes, box_off):
+    """Checks the scenes' layout.  -> (seg, box_off) as contiguous int64 numpy arrays of B + 1 entries."""
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or (
+            points.shape[0] > 1 and points.stride(1) != 1) or points.stride(0) < points.shape[1]:
+        raise ValueError("points must be a float32 [rows, D >= 3] tensor with unit column stride")
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] < 7 or not boxes.is_contiguous():
+        raise ValueError("boxes must be a contiguous float32 [M, W >= 7] tensor")
+    seg = np.ascontiguousarray([0, points.shape[0]] if seg is None else seg, np.int64).reshape(-1)
+    if box_off is None:
+        if len(seg) != 2:
+            raise ValueError("box_off may be omitted for a single scene only")
+        box_off = [0, boxes.shape[0]]
+    box_off = np.ascontiguousarray(box_off, np.int64).reshape(-1)
+    if len(seg) < 2 or seg[0] != 0 or seg[-1] != points.shape[0] or (np.diff(seg) < 0).any():
+        raise ValueError("seg must ascend from 0 to the number of rows")
+    if len(box_off) != len(seg) or box_off[0] != 0 or box_off[-1] != boxes.shape[0] or (np.diff(box_off) < 0).any():
+        raise ValueError("box_off must have one entry per seg entry and ascend from 0 to the number of boxes")
+    return seg, box_off
+
+
+def _owner_launch(points, seg, boxes, box_off, out=None):
+    """ud_points_in_boxes on the current stream.  -> (owner int32 [rows], device offsets (seg, box_off))."""
+    rows, D = points.shape
+    B = len(seg) - 1
+    offs_d = torch.from_numpy(np.concatenate([seg, box_off])).to(points.device)
+    seg_d, box_off_d = offs_d[:B + 1], offs_d[B + 1:]
+    owner = torch.empty(rows, dtype=torch.int32, device=points.device) if out is None else out
+    if owner.dtype != torch.int32 or owner.shape != (rows,) or not owner.is_contiguous() or owner.device != points.device:
+        raise ValueError("out must be a contiguous int32 [rows] tensor on the points' device")
+    _lib.ud.ud_points_in_boxes(points, rows, D, points.stride(0) if rows > 1 else D, seg.ctypes.data, seg_d, boxes,
+                               boxes.shape[1], boxes.shape[1], box_off.ctypes.data, box_off_d, B, owner,
+                               _lib.stream_of(points))
+    return owner, (seg_d, box_off_d)
+
+
+def _device_boxes(boxes, device):
+    if torch.is_tensor(boxes):
+        return boxes.to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(boxes, np.float32)).to(device)
+
+
+def points_in_boxes(points, seg, boxes, box_off=None, out=None):
+    """OpenPCDet's points_in_boxes_gpu for scenes lying back to back: ``points`` f32 [rows, D >= 3] on the GPU, ``seg``
+    the scenes' row offsets (B + 1 ints), ``boxes`` f32 [Mtot, W >= 7] (a device tensor or a host array), ``box_off``
+    the scenes' box offsets; for a single scene ``seg`` and ``box_off`` may be None.  -> owner int32 [rows]: the index,
+    within its scene, of the lowest-numbered box that contains the row, or -1 (the paste's inside test, float32; a
+    non-finite box contains nothing, a non-finite row gets -1).  One launch on the current stream, no host wait;
+    ``out``: the int32 tensor to fill."""
+    _lib.require_gpu(points)
+    boxes = _device_boxes(boxes, points.device)
+    seg, box_off = _scene_offsets(points, seg, boxes, box_off)
+    return _owner_launch(points, seg, boxes, box_off, out)[0]
+
+
+def _extract_objects(points, seg, boxes, box_off):
+    """Every box's points as a box-centred cloud: ud_points_in_boxes, ud_gt_db_count -> ONE readback of the counts ->
+    ud_gt_db_extract, the shape of lidar_prep._two_pass, on the current stream.
+    -> (clouds f32 [total, D] in (scene, box) order, rows per box int64 numpy [Mtot])."""
+    rows, D = points.shape
+    M, W = boxes.shape
+    B = len(seg) - 1
+    device = points.device
+    stream = torch.cuda.current_stream(device)
+    hs = stream.cuda_stream
+    owner, (seg_d, box_off_d) = _owner_launch(points, seg, boxes, box_off)
+    ws_bytes = int(_lib.load().ud_gt_db_workspace_bytes(rows, M))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    counts_d = torch.empty(M + 1, dtype=torch.int64, device=device)
+    _lib.ud.ud_gt_db_count(owner, rows, seg.ctypes.data, seg_d, box_off.ctypes.data, box_off_d, B, counts_d, ws, ws_bytes,
+                           hs)
+    counts_h = torch.empty(M + 1, dtype=torch.int64, pin_memory=True)
+    counts_h.copy_(counts_d, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    ev.synchronize()                                    # this stream's work only
+    counts = counts_h.numpy().copy()
+    out = torch.empty((int(counts[-1]), D), dtype=torch.float32, device=device)
+    _lib.ud.ud_gt_db_extract(points, rows, D, points.stride(0) if rows > 1 else D, boxes, W, W, M, counts.ctypes.data, out,
+                             out.shape[0], ws, ws_bytes, hs)
+    return out, counts[:-1]
+
+
+class ObjectDatabaseBuilder:
+    """OpenPCDet's create_groundtruth_database on the device: per scene, which of ALL its boxes owns each point
+    (points_in_boxes; the lowest index wins a shared point), then every box's points with the box centre subtracted.
+    Afterwards the objects whose name is not in ``class_names`` (or not in ``used_classes``, when given) are left out --
+    an ignored box still owns its points.  A box without points stays, with zero rows.  ``finish`` gives the
+    device-resident ``ObjectDatabase`` the sampler and the paste read; the clouds never visit the host."""
+
+    def __init__(self, class_names, device="cuda", used_classes=None):
+        self.class_names = [str(c) for c in class_names]
+        self.used_classes = None if used_classes is None else {str(c) for c in used_classes}
+        self.device = torch.device(device)
+        self.D = self.W = None
+        self.scenes = 0
+        self._clouds, self._rows, self._boxes, self._names, self._image_idx, self._gt_idx = [], [], [], [], [], []
+
+    def _check_scene(self, scene, D, W):
+        """One scene's arguments, host only.  -> (points, boxes f32 numpy [M, W], names object array [M], D, W)."""
+        points, boxes = scene["points"], scene["gt_boxes"]
+        names, labels = scene.get("gt_names"), scene.get("gt_labels")
+        if (names is None) == (labels is None):
+            raise ValueError("pass exactly one of gt_names and gt_labels")
+        if not torch.is_tensor(points):
+            points = np.asarray(points)
+        f32 = torch.float32 if torch.is_tensor(points) else np.float32
+        if points.ndim != 2 or points.shape[1] < 3 or points.dtype != f32:
+            raise ValueError("points must be float32 [N, D >= 3]")
+        if D is not None and points.shape[1] != D:
+            raise ValueError(f"points have {points.shape[1]} columns, the scenes before {D}")
+        boxes = np.asarray(boxes.cpu() if torch.is_tensor(boxes) else boxes, np.float32)
+        boxes = boxes.reshape(0, W or 7) if boxes.size == 0 and boxes.ndim != 2 else boxes
+        if boxes.ndim != 2 or boxes.shape[1] < 7:
+            raise ValueError("gt_boxes must be [M, W >= 7]")
+        if W is not None and boxes.shape[1] != W:
+            raise ValueError(f"gt_boxes have {boxes.shape[1]} columns, the scenes before {W}")
+        if names is None:
+            labels = np.asarray(labels).reshape(-1)
+            if len(labels) and (not np.issubdtype(labels.dtype, np.integer) or labels.min() < 0
+                                or labels.max() >= len(self.class_names)):
+                raise ValueError(f"unknown label: gt_labels must be integers in 0 .. {len(self.class_names) - 1}")
+            names = np.asarray(self.class_names, object)[labels.astype(np.int64)]
+        names = np.asarray([str(n) for n in np.asarray(names, object).reshape(-1)], object)
+        if len(names) != len(boxes):
+            raise ValueError(f"{len(boxes)} boxes, {len(names)} names / labels")
+        return points, boxes, names, points.shape[1], boxes.shape[1]
+
+    def add_scene(self, points, gt_boxes, gt_names=None, gt_labels=None, sample_idx=None):
+        """One scene: ``points`` [N, D] (a device tensor or a host array; the sweeps already merged into the key frame),
+        ``gt_boxes`` [M, W >= 7] with every column kept, exactly one of ``gt_names`` / ``gt_labels`` (indices into
+        class_names), ``sample_idx`` for infos()["image_idx"] (default: the scene's running number)."""
+        self.add_scenes([{"points": points, "gt_boxes": gt_boxes, "gt_names": gt_names, "gt_labels": gt_labels,
+                          "sample_idx": sample_idx}])
+
+    def add_scenes(self, scenes):
+        """Several scenes (dicts with add_scene's arguments as keys) in one launch group with one readback."""
+        D, W, checked = self.D, self.W, []
+        for scene in scenes:                                # every argument check comes before any device work
+            pts, boxes, names, D, W = self._check_scene(scene, D, W)
+            checked.append((pts, boxes, names, scene.get("sample_idx")))
+        if not checked:
+            return
+        device = _lib.require_gpu_device(self.device)
+        clouds = []
+        for pts, *_ in checked:
+            if torch.is_tensor(pts) and pts.is_cuda:
+                clouds.append(pts)
+            else:
+                clouds.append((pts if torch.is_tensor(pts) else torch.from_numpy(np.ascontiguousarray(pts))).to(device))
+        points = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
+        if points.shape[0] > 1 and points.stride(1) != 1:
+            points = points.contiguous()
+        boxes = np.concatenate([b for _, b, _, _ in checked])
+        seg = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+        box_off = np.concatenate([[0], np.cumsum([len(b) for _, b, _, _ in checked])]).astype(np.int64)
+        with torch.cuda.device(points.device):
+            out, rows = _extract_objects(points, seg, torch.from_numpy(boxes).to(points.device), box_off)
+        self.D, self.W = D, W
+        self._clouds.append(out)
+        self._rows.append(rows)
+        self._boxes.append(boxes)
+        for _, b, names, idx in checked:
+            self._names.append(names)
+            self._image_idx.append(np.full(len(b), self.scenes if idx is None else idx, object))
+            self._gt_idx.append(np.arange(len(b)))
+            self.scenes += 1
+
+    def _objects(self):
+        """-> (rows, boxes, names, class ids, class-filter mask) of every box added so far, in (scene, box) order."""
+        if not self._clouds:
+            raise ValueError("no scene has been added")
+        names = np.concatenate(self._names)
+        ids = np.array([self.class_names.index(n) if n in self.class_names else -1 for n in names], np.int64)
+        keep = ids >= 0
+        if self.used_classes is not None:
+            keep &= np.array([n in self.used_classes for n in names], bool)
+        return np.concatenate(self._rows), np.concatenate(self._boxes), names, ids, keep
+
+    def infos(self):
+        """OpenPCDet's dbinfos layout {class: [{"name", "image_idx", "gt_idx", "box3d_lidar", "num_points_in_gt"}]} of
+        the objects kept by the class filter (no "path": the clouds are in the database, not in files)."""
+        rows, boxes, names, _, keep = self._objects()
+        image_idx, gt_idx = np.concatenate(self._image_idx), np.concatenate(self._gt_idx)
+        out = {}
+        for i in np.nonzero(keep)[0]:
+            out.setdefault(str(names[i]), []).append({"name": str(names[i]), "image_idx": image_idx[i],
+                                                      "gt_idx": int(gt_idx[i]), "box3d_lidar": boxes[i].copy(),
+                                                      "num_points_in_gt": int(rows[i])})
+        return out
+
+    def finish(self, filter_by_min_points_cfg=None, name=None):
+        """-> the ObjectDatabase of the kept objects: the class filter, then ``filter_by_min_points_cfg`` (["car:5",
+        ...]: the objects of a named class with fewer points are dropped, as ObjectDatabase.from_arrays does).  The
+        clouds stay on the device; offsets, boxes and class ids are host arrays."""
+        rows, boxes, _, ids, keep = self._objects()
+        for cname, least in _parse_cfg(filter_by_min_points_cfg):
+            if cname in self.class_names:
+                keep &= ~((ids == self.class_names.index(cname)) & (rows < least))
+        points = self._clouds[0] if len(self._clouds) == 1 else torch.cat(self._clouds)
+        if not keep.all():
+            points = points[torch.from_numpy(np.repeat(keep, rows)).to(points.device)]
+        offsets = np.concatenate([[0], np.cumsum(rows[keep])]).astype(np.int64)
+        return ObjectDatabase(points, offsets, boxes[keep], ids[keep], self.class_names, points.device, name)
 
 
 class GTSampling:

@@ -2,7 +2,8 @@
 ones before it: staging -> lidar_prep -> gt_paste -> image_affine -> jpeg -> collate."""
 from ..config import IMG_DIM                                                                        # noqa: F401
 from .collate import collate_fn, lidar_prep_host_clouds                                             # noqa: F401
-from .gt_paste import GTSampling, ObjectDatabase, append_pasted, gt_paste, lidar_paste_host_clouds  # noqa: F401
+from .gt_paste import (GTSampling, ObjectDatabase, ObjectDatabaseBuilder, append_pasted, gt_paste,  # noqa: F401
+                       lidar_paste_host_clouds, points_in_boxes)
 from .image_affine import (IMG_MEAN, IMG_STD, TO_RGB, ImageAffineTransformation, ida_matrix,        # noqa: F401
                            image_affine, image_affine_host_frames, image_normalize, plan_frames, resample_table,
                            rotate_constants)

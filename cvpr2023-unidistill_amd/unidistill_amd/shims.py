@@ -11,7 +11,8 @@ height_compression.py, the BEVFusion_*_exp files) import and run on this library
   mmcv.Config                                             -> attribute dict
   iou3d_nms_cuda.nms_gpu                                  -> ops.nms.nms_gpu (rotated-BEV NMS, ud_nms_rotated_bev)
   iou3d_nms_cuda.boxes_iou3d_pairs                        -> ops.det_loss.rotated_iou3d (additive: nothing in the reference calls it)
-  roiaware_pool3d_cuda                                    -> import-time stub (unused path; calling raises)
+  roiaware_pool3d_cuda.points_in_boxes_gpu                -> ops.gt_paste.points_in_boxes (ud_points_in_boxes)
+  roiaware_pool3d_cuda, its other six names               -> import-time stubs (RoI-aware pooling: unused path; calling raises)
 Registry-style mmdet.core.* names the reference merely imports are provided as inert placeholders.
 """
 import sys
@@ -69,6 +70,21 @@ def _unavailable(what):
     return fn
 
 
+def _points_in_boxes_gpu(boxes, points, out):
+    """roiaware_pool3d_cuda.points_in_boxes_gpu(boxes [B, T, 7], points [B, M, 3], out int32 [B, M]) as
+    roiaware_pool3d_utils.py:49-51 calls it: fills ``out`` in place with each point's lowest containing box, or -1."""
+    import torch
+    from .ops import gt_paste
+    B, T = boxes.shape[:2]
+    M = points.shape[1]
+    direct = out.dtype == torch.int32 and out.is_contiguous()
+    got = gt_paste.points_in_boxes(points.float().contiguous().view(B * M, 3), [b * M for b in range(B + 1)],
+                                   boxes.float().contiguous().view(B * T, boxes.shape[2]), [b * T for b in range(B + 1)],
+                                   out=out.view(B * M) if direct else None)
+    if not direct:
+        out.copy_(got.view(B, M))
+
+
 class _Registry:
     def register_module(self, *a, **k):
         return lambda cls: cls
@@ -84,10 +100,10 @@ def install():
     _leaf("unidistill.layers.head.det3d.generate_proposals.iou3d_nms_cuda",
           nms_gpu=nms.nms_gpu, boxes_iou_bev_gpu=nms.boxes_iou_bev_gpu, boxes_iou3d_pairs=det_loss.rotated_iou3d,
           nms_normal_gpu=_unavailable("nms_normal_gpu"))
-    _leaf("unidistill.utils.det3d_utils.roiaware_pool3d_cuda",
+    _leaf("unidistill.utils.det3d_utils.roiaware_pool3d_cuda", points_in_boxes_gpu=_points_in_boxes_gpu,
           **{n: _unavailable("roiaware_pool3d_cuda." + n) for n in (
-              "points_in_boxes_cpu", "points_in_boxes_gpu", "bev_in_boxes_cpu", "bev_in_boxes_gpu",
-              "points_in_boxes_bev_gpu", "forward", "backward")})
+              "points_in_boxes_cpu", "bev_in_boxes_cpu", "bev_in_boxes_gpu", "points_in_boxes_bev_gpu", "forward",
+              "backward")})
     # --- spconv
     _module("spconv")
     _module("spconv.core", ConvAlgo=sp.ConvAlgo)

@@ -1184,6 +1184,42 @@ int ud_lidar_paste_compact(const float* pts, int64_t rows, int D, const int64_t*
                            const int64_t* counts_host, const int64_t* counts, int64_t nmax, int compact, float* out,
                            int64_t out_rows, void* workspace, size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- Building the GT-sampling object database (csrc/gt_database.hip) ---------------------------------
+ * OpenPCDet's create_groundtruth_database on the device: which box owns each point of whole scenes, then every box's
+ * points as a box-centred cloud.  The scenes lie back to back: pts f32, row i at pts + i * pts_stride (floats,
+ * pts_stride >= D >= 3; columns 0..2 are x, y, z), seg[B + 1] row offsets with seg[0] == 0 and seg[B] == rows; boxes
+ * f32, box g at boxes + g * box_stride (box_stride >= W >= 7; x, y, z, dx, dy, dz, yaw, the rest not read),
+ * box_off[B + 1] with box_off[0] == 0; n_boxes = box_off[B] <= 262 144.  Offsets are given on the host (validation,
+ * grid size) and on the device.
+ *   ud_points_in_boxes   owner i32 [rows]: the index WITHIN ITS SAMPLE of the lowest-numbered box that contains the row,
+ *                        or -1 (points_in_boxes_gpu, whose loop leaves at the first hit).  The inside test is the paste's
+ *                        (ud_lidar_paste_*, above), float32.  A box with a non-finite entry among its first 7 contains
+ *                        nothing; a row with a non-finite x, y or z gets -1.  One launch, any number of boxes per sample.
+ *   ud_gt_db_count       counts i64 [n_boxes + 1] (device): rows owned by each box, in (sample, box) order, and their
+ *                        total in counts[n_boxes].  An owner outside its sample's boxes counts as -1.  Leaves the hit list
+ *                        in the workspace for ud_gt_db_extract: same workspace, same stream, nothing in between.
+ *   ud_gt_db_extract     counts_host = counts read back.  out f32 [total][D], dense: the boxes' clouds back to back in
+ *                        (sample, box) order, inside a box ascending by input row (a stable partition); columns 0..2 are
+ *                        x - cx, y - cy, z - cz, one float32 subtraction each, every other column is copied bit for bit.
+ *                        No row at or beyond out_rows is written.
+ *   Three launches for the count, three per 9 key bits (stable radix sort of the hits by box) plus one for the extract.
+ *   Integer counting only, every output element written once: bitwise reproducible.  ud_gt_db_workspace_bytes(rows,
+ *   n_boxes) -> bytes (0 for rows == 0 or an invalid size).
+ *   UD_ERR_INVALID_ARG, nothing launched: D < 3, W < 7, a stride below D / W, offsets that descend or do not span
+ *   0 .. rows, rows >= 2^31, too many boxes, counts_host negative / not summing to counts_host[n_boxes] / above rows,
+ *   out_rows below the total, a NULL pointer to something non-empty.  All sizes zero: UD_OK, nothing done. */
+int ud_points_in_boxes(const float* pts, int64_t rows, int D, int64_t pts_stride, const int64_t* seg_host,
+                       const int64_t* seg_dev, const float* boxes, int W, int64_t box_stride,
+                       const int64_t* box_off_host, const int64_t* box_off_dev, int B, int32_t* owner,
+                       ud_stream_t stream);
+size_t ud_gt_db_workspace_bytes(int64_t rows, int64_t n_boxes);
+int ud_gt_db_count(const int32_t* owner, int64_t rows, const int64_t* seg_host, const int64_t* seg_dev,
+                   const int64_t* box_off_host, const int64_t* box_off_dev, int B, int64_t* counts, void* workspace,
+                   size_t workspace_bytes, ud_stream_t stream);
+int ud_gt_db_extract(const float* pts, int64_t rows, int D, int64_t pts_stride, const float* boxes, int W,
+                     int64_t box_stride, int64_t n_boxes, const int64_t* counts_host, float* out, int64_t out_rows,
+                     void* workspace, size_t workspace_bytes, ud_stream_t stream);
+
 /* ---- Depth metric of the camera student's lift (csrc/depth_metric.hip) ------------------------------
  * The monocular-depth figures of the lift against the LiDAR minimum depth, accumulated on the device.
  *   logits f32[BN, D, fH, fW] through element strides (sn, sc, sh, sw), D <= 256: NCHW or the channels-last slice
