@@ -437,14 +437,23 @@ class ValidationStep(nn.Module):
 
     ``depth_metric``: an ``evaluation.DepthMetric``; the eval forward's own depth logits (inside ``weights()``, so the
     averaged weights are the ones measured) and the batch's LiDAR minimum depth are added to it, on the device.  Needs a
-    model with a camera encoder and a batch with 'points' and 'mats_dict'.  ``None``: the step is unchanged."""
+    model with a camera encoder and a batch with 'points' and 'mats_dict'.  ``None``: the step is unchanged.
 
-    def __init__(self, model, evaluator, weights=None, depth_metric=None):
+    ``tta``: flip test-time augmentation (ops/tta.py): ``"double_flip"`` or a list of (flip_dx, flip_dy) views.
+    The batch goes through the model once as V * B samples, the head merges the views' maps on the device, and the B merged
+    ``pred_dicts`` go to the evaluator.  Needs a point-cloud range symmetric about 0 on every flipped axis.  With
+    ``depth_metric`` the depth of view 0 is measured, which must be the unflipped one.  ``None``: the step is unchanged."""
+
+    def __init__(self, model, evaluator, weights=None, depth_metric=None, tta=None):
         super().__init__()
         self.model = model
         self.evaluator = evaluator
         self.weights = weights
         self.depth_metric = depth_metric
+        self.tta_views = None
+        if tta is not None:
+            from .ops import tta as T
+            self.tta_views = T.resolve_views(tta)
 
     def _check_depth_inputs(self, batch):
         if self.model.camera_encoder is None:
@@ -453,28 +462,51 @@ class ValidationStep(nn.Module):
             raise ValueError("depth_metric is set, but the batch carries no LiDAR 'points' (or no 'mats_dict') to build the "
                              "depth labels from: a camera-only batch has no depth to measure against")
 
-    def _forward_with_depth_metric(self, batch, points):
-        out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None, return_depth_logits=True)
+    def _forward_with_depth_metric(self, batch, points, inputs):
+        """``inputs``: the batch the model sees -- ``batch`` itself, or its views, of which the first B samples are ``batch``."""
+        out = self.model(points, inputs.get("imgs"), inputs.get("mats_dict"), None, return_depth_logits=True)
         dmin = self.model.camera_encoder.backbone.lidar_depth_labels(batch["points"], batch["mats_dict"])[0]
-        self.depth_metric.add_batch(out.pop("depth_logits"), dmin)
+        logits = out.pop("depth_logits")
+        if inputs is not batch:                 # view-major: the first B * ncam images are view 0
+            logits = logits[:dmin.numel() // (dmin.shape[-2] * dmin.shape[-1])]
+        self.depth_metric.add_batch(logits, dmin)
         return out
+
+    def _check_tta(self):
+        from .ops import tta as T
+        head = self.model.det_head.dense_head
+        T.check_symmetric_range(head.point_cloud_range, self.tta_views)
+        if self.depth_metric is not None and self.tta_views[0] != (0, 0):
+            raise ValueError(f"depth_metric measures view 0 of the test-time augmentation, which must be the unflipped view "
+                             f"(0, 0); the views are {self.tta_views}")
+        return head
 
     def forward(self, batch, sample_ids, lidar_to_global):
         if self.depth_metric is not None:
             self._check_depth_inputs(batch)
-        points = batch.get("points")
+        inputs, head = batch, None
+        if self.tta_views is not None:
+            from .ops import tta as T
+            head = self._check_tta()
+            inputs = T.flip_views(batch, self.tta_views)
+        points = inputs.get("points")
         if points is not None and not isinstance(points, (list, tuple)):
             points = [p for p in points]
         was_training = self.model.training
         self.model.eval()
+        views_before = None if head is None else head.tta_views
         try:
+            if head is not None:
+                head.tta_views = self.tta_views
             weights = contextlib.nullcontext() if self.weights is None else self.weights()
             with weights, torch.no_grad():
                 if self.depth_metric is not None:
-                    out = self._forward_with_depth_metric(batch, points)
+                    out = self._forward_with_depth_metric(batch, points, inputs)
                 else:
-                    out = self.model(points, batch.get("imgs"), batch.get("mats_dict"), None)
+                    out = self.model(points, inputs.get("imgs"), inputs.get("mats_dict"), None)
         finally:
+            if head is not None:
+                head.tta_views = views_before
             self.model.train(was_training)
         self.evaluator.add_batch(sample_ids, out["pred_dicts"], lidar_to_global)
         return out["pred_dicts"]

@@ -1246,6 +1246,29 @@ int ud_depth_metric_accumulate(const float* logits, int64_t sn, int64_t sc, int6
                                const double* range_edges, int n_ranges, double* state, void* workspace,
                                size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- Flip test-time augmentation: merge of the head maps of V flipped views (csrc/tta_merge.hip) -----
+ * One launch for all T <= 8 tasks and their seven heads; nothing synchronises with the host, no workspace, no atomics,
+ * bitwise reproducible.
+ *   heads / strides      HOST arrays [T*7] / [T*7*3] as for ud_proposal_layer (hm, reg, height, dim, rot, vel, iou; fp32,
+ *                        logical shape [V*B, c, H, W]; (batch, channel, pixel) element strides: NCHW planes or channel slices
+ *                        of a channels-last map).  View v of sample b is row v * B + b.  A NULL pointer: the head is absent
+ *                        and nothing is written for it; hm must be present.  c = num_classes[t] for hm, else 2 1 3 2 2 1.
+ *   outs / out_strides   the same two tables for the outputs, logical shape [B, c, H, W] (strides below 2^31).
+ *   flips                HOST int [V*2]: (flip_dx, flip_dy) of each view, 1 <= V <= 4, any combinations in any order.
+ * Output pixel (y, x) reads pixel (flip_dy ? H-1-y : y, flip_dx ? W-1-x : x) of view v; flip_dx mirrors the x axis.  The
+ * un-flipped terms are added for v = 0 .. V-1 in that order, starting from view 0's term, and the sum is multiplied by the
+ * fp32 value 1 / V.  Terms: reg[0]: flip_dx ? 1 - r : r; reg[1]: flip_dy ? 1 - r : r; rot[0] (sin) and vel[1]: negated under
+ * flip_dy; rot[1] (cos) and vel[0]: negated under flip_dx; height, iou: as they are; dim: as it is when no_log, else exp(d),
+ * and the output is log(mean), not clamped; hm: sigmoid(h) = 1 / (1 + exp(-h)), and the output is logit(mean) = log(m) -
+ * log1p(-m): -inf when the mean rounds to 0, +inf when it rounds to 1, never NaN for finite inputs.  The sums of hm and of
+ * a logarithmic dim, and their way back, are carried in double and rounded to fp32 once; all other heads are fp32 throughout.
+ * The rules are exact for a BEV range that is symmetric about 0 on each flipped axis (the caller's check).
+ * UD_ERR_INVALID_ARG with nothing launched: V outside 1..4, B, T, H, W out of range, a missing table, hm or output pointer,
+ * a negative stride; UD_ERR_UNSUPPORTED: more than 256 channels in all, or B*H*W*channels >= 2^31. */
+int ud_tta_merge(const float* const* heads, const long long* strides, float* const* outs, const long long* out_strides,
+                 const int* num_classes, const int* flips, int V, int B, int T, int H, int W, int no_log,
+                 ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
