@@ -7,9 +7,13 @@
 // a one-hot class heat map is written.  The tensor-op formulation (layers/center_head.py) issues ~180
 // launches per step; here one workgroup owns one (task, sample) pair:
 //   boxes -> LDS, task members ranked by (class offset, index); per member one wave picks the k
-//   smallest of the 81 window candidates (the k <= 9 nearest anchors of a point on the regular anchor
-//   grid lie within +-4 cells of the clamped nearest cell); positives are bits of an LDS bitmap whose
-//   prefix popcount gives the ascending slot; nearest-box search, encoding and heat map follow.
+//   smallest of the 81 window candidates.  The window is the 9 nearest columns x the 9 nearest rows,
+//   shifted so that it lies wholly inside the grid: the squared distance is a column term plus a row
+//   term, so a cell among the k nearest has (column rank) x (row rank) <= k <= 9 and its column and
+//   row are each among the 9 nearest -- for any finite centre, however far outside the range (a window
+//   clipped at the border instead loses cells once the centre is 8 or more cells outside).  Positives
+//   are bits of an LDS bitmap whose prefix popcount gives the ascending slot; nearest-box search,
+//   encoding and heat map follow.
 // Integer outputs are bit-identical to the tensor-op path; float encodings use the same operations.
 #include "ud_common.h"
 #include "ud_prof.h"
@@ -60,9 +64,10 @@ __global__ __launch_bounds__(256) void k_assign_targets(AssignArgs a, const floa
   __syncthreads();
   const int last = s_last;
   for (int m = tid; m < a.M; m += 256) {
-    long long cls = (long long)box[m * a.cols + a.cols - 1];
-    cls = cls < 0 ? 0 : (cls > kMaxClasses - 1 ? kMaxClasses - 1 : cls);
-    const bool member = m <= last && a.task_of[cls] == t;
+    // an id outside the class table belongs to no task (the reference matches ids by equality)
+    const long long id = (long long)box[m * a.cols + a.cols - 1];
+    const int cls = id < 0 || id > kMaxClasses - 1 ? 0 : (int)id;
+    const bool member = m <= last && id == cls && a.task_of[cls] == t;
     coff[m] = member ? a.off_of[cls] : -1;
   }
   __syncthreads();
@@ -82,21 +87,19 @@ __global__ __launch_bounds__(256) void k_assign_targets(AssignArgs a, const floa
   // the topk nearest anchors of every member: one wave per member, 81 window candidates
   for (int r = wave; r < nm; r += 4) {
     const float px = mcx[r], py = mcy[r];
-    int cxi = (int)rintf(px / a.osf), cyi = (int)rintf(py / a.osf);
-    cxi = cxi < 0 ? 0 : (cxi > a.w - 1 ? a.w - 1 : cxi);
-    cyi = cyi < 0 ? 0 : (cyi > a.h - 1 ? a.h - 1 : cyi);
+    // first column / row of the window: the 9 nearest (lower one on a tie), shifted into the grid
+    const int x0 = (int)fminf(fmaxf(ceilf(px / a.osf - 4.5f), 0.f), (float)(a.w - 9));
+    const int y0 = (int)fminf(fmaxf(ceilf(py / a.osf - 4.5f), 0.f), (float)(a.h - 9));
     unsigned long long key[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int c = lane + 64 * s;
       key[s] = ~0ull;
       if (c < 81) {
-        const int ix = cxi + (c % 9) - 4, iy = cyi + (c / 9) - 4;
-        if (ix >= 0 && ix < a.w && iy >= 0 && iy < a.h) {
-          const float dx = (float)ix * a.osf - px, dy = (float)iy * a.osf - py;
-          const float d = dx * dx + dy * dy;
-          key[s] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(iy * a.w + ix);
-        }
+        const int ix = x0 + (c % 9), iy = y0 + (c / 9);
+        const float dx = (float)ix * a.osf - px, dy = (float)iy * a.osf - py;
+        const float d = dx * dx + dy * dy;
+        key[s] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(iy * a.w + ix);
       }
     }
     for (int it = 0; it < a.topk; ++it) {

@@ -226,20 +226,23 @@ class FCOSAssigner:
         return ind, sgt, mask, pos, gid
 
     def _assign_windowed(self, anchors, pcx, pcy, mem, w, h, K, topk):
-        """Same result without the [TB, M, A] distance tensor (124 MB at B=4): the k <= 9 anchors nearest
-        to a point lie within +-4 cells of the (clamped) nearest cell of the regular anchor grid, so the
-        top-k runs over 81 candidates per box; positives are the <= M*k selected anchors, sorted and
+        """Same result without the [TB, M, A] distance tensor (124 MB at B=4): the top-k runs over the 81
+        candidates of a 9 x 9 window per box.  The window is the 9 nearest columns x the 9 nearest rows of
+        the regular anchor grid (the lower one on a tie), shifted so that it lies wholly inside the grid.
+        The squared distance is a column term plus a row term, so a cell among the k <= 9 nearest has
+        (column rank) x (row rank) <= k: its column and its row are each among the 9 nearest, for any finite
+        centre, however far outside the range.  Positives are the <= M*k selected anchors, sorted and
         de-duplicated; the nearest box is searched only at those positives."""
         dev = anchors.device
         TB, M = pcx.shape
         s = float(self.out_size_factor)
         inf = float("inf")
-        cxi = torch.round(pcx / s).clamp(0, w - 1).long()
-        cyi = torch.round(pcy / s).clamp(0, h - 1).long()
-        off = torch.arange(-4, 5, device=dev)
-        ix = cxi[:, :, None, None] + off[None, None, None, :]                            # [TB,M,1,9]
-        iy = cyi[:, :, None, None] + off[None, None, :, None]                            # [TB,M,9,1]
-        ok = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h) & mem[:, :, None, None]
+        x0 = torch.ceil(pcx / s - 4.5).clamp(0, w - 9).long()
+        y0 = torch.ceil(pcy / s - 4.5).clamp(0, h - 9).long()
+        off = torch.arange(9, device=dev)
+        ix = x0[:, :, None, None] + off[None, None, None, :]                             # [TB,M,1,9]
+        iy = y0[:, :, None, None] + off[None, None, :, None]                             # [TB,M,9,1]
+        ok = mem[:, :, None, None]
         d = (ix.float() * s - pcx[:, :, None, None]) ** 2 + (iy.float() * s - pcy[:, :, None, None]) ** 2
         d = torch.where(ok, d, torch.full_like(d, inf)).reshape(TB, M, 81)
         aid = (iy * w + ix).reshape(TB, M, 81)
@@ -284,7 +287,9 @@ class FCOSAssigner:
         A = anchors.shape[0]
         ncmax = max(len(c) for c in self.task_classes)
         task_of, off_of = self._class_tables(dev)
-        cls = gt_boxes[:, :, -1].long().clamp(0, task_of.numel() - 1)
+        cid = gt_boxes[:, :, -1].long()
+        cls = cid.clamp(0, task_of.numel() - 1)
+        in_table = cid == cls                   # an id outside the class table belongs to no task
         box = gt_boxes[:, :, :-1]
         idx = torch.arange(M, device=dev)
         # rows up to the last one that does not sum to zero are kept (row 0 always is)
@@ -298,7 +303,7 @@ class FCOSAssigner:
         yaw = limit_period(box[:, :, 6], offset=0.5, period=math.pi * 2)
         # class offset inside each task, -1 for boxes of other tasks / invalid rows: [T,B,M] -> [TB,M]
         tsel = torch.arange(T, device=dev)[:, None, None]
-        member = valid[None] & (task_of[cls][None] == tsel)
+        member = (valid & in_table)[None] & (task_of[cls][None] == tsel)
         coff = torch.where(member, off_of[cls][None].expand(T, B, M), torch.full((T, B, M), -1, device=dev))
         coff = coff.reshape(T * B, M)
         member = member.reshape(T * B, M)
