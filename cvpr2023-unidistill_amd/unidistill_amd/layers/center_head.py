@@ -603,6 +603,7 @@ class CenterHead(nn.Module):
     # Flip test-time augmentation (ops/tta.py): a list of (flip_dx, flip_dy) views, e.g. tta.DOUBLE_FLIP.  When set, in eval
     # mode, without distill and with a proposal layer, forward takes its input as the V * B view-major batch of
     # tta.flip_views and hands the merged maps of B samples to the proposal layer.  None: forward is unchanged.
+    # Views (rot_deg, scale, flip_dx, flip_dy), e.g. tta.views(rotations=(0, 7.5, -7.5)), are merged by resampling.
     tta_views = None
 
     def __init__(self, dataset_name, tasks, target_assigner, proposal_layer, input_channels,
@@ -666,12 +667,12 @@ class CenterHead(nn.Module):
         if self.proposal_layer is None:
             return ret
         if self.tta_views is not None:
-            # the batch holds the views of B samples, view-major (ops/tta.py): one kernel un-flips and averages the maps
+            # the batch holds the views of B samples, view-major (ops/tta.py): one kernel un-flips and averages the maps (a
+            # list of pure flips, after check_symmetric_range), or -- rotation / scale views -- resamples them onto the
+            # unrotated grid of point_cloud_range and brings the values back into the original frame
             from ..ops import tta
-            views = tta.resolve_views(self.tta_views)
-            tta.check_symmetric_range(self.point_cloud_range, views)
-            ret["multi_head_features"] = tta.flip_merge(
-                ret["multi_head_features"], views, no_log=self.proposal_layer.no_log,
+            ret["multi_head_features"] = tta.merge(
+                ret["multi_head_features"], self.tta_views, self.point_cloud_range, no_log=self.proposal_layer.no_log,
                 nbox=9 if self.proposal_layer.dataset_name == "nuscenes" else 7)
         return self.proposal_layer.generate_predicted_boxes(ret, {})
 

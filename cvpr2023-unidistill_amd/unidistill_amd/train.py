@@ -439,9 +439,10 @@ class ValidationStep(nn.Module):
     averaged weights are the ones measured) and the batch's LiDAR minimum depth are added to it, on the device.  Needs a
     model with a camera encoder and a batch with 'points' and 'mats_dict'.  ``None``: the step is unchanged.
 
-    ``tta``: flip test-time augmentation (ops/tta.py): ``"double_flip"`` or a list of (flip_dx, flip_dy) views.
+    ``tta``: test-time augmentation (ops/tta.py): ``"double_flip"``, a list of (flip_dx, flip_dy) views,
+    or a list of up to 16 (rot_deg, scale, flip_dx, flip_dy) views (``ops.tta.views``) whose view 0 is a flip or the identity.
     The batch goes through the model once as V * B samples, the head merges the views' maps on the device, and the B merged
-    ``pred_dicts`` go to the evaluator.  Needs a point-cloud range symmetric about 0 on every flipped axis.  With
+    ``pred_dicts`` go to the evaluator.  A list of flips needs a point-cloud range symmetric about 0 on every flipped axis.  With
     ``depth_metric`` the depth of view 0 is measured, which must be the unflipped one.  ``None``: the step is unchanged."""
 
     def __init__(self, model, evaluator, weights=None, depth_metric=None, tta=None):
@@ -475,8 +476,9 @@ class ValidationStep(nn.Module):
     def _check_tta(self):
         from .ops import tta as T
         head = self.model.det_head.dense_head
-        T.check_symmetric_range(head.point_cloud_range, self.tta_views)
-        if self.depth_metric is not None and self.tta_views[0] != (0, 0):
+        if all(len(v) == 2 for v in self.tta_views):        # the flip path; rotation / scale views are resampled on any range
+            T.check_symmetric_range(head.point_cloud_range, self.tta_views)
+        if self.depth_metric is not None and not T.is_identity(self.tta_views[0]):
             raise ValueError(f"depth_metric measures view 0 of the test-time augmentation, which must be the unflipped view "
                              f"(0, 0); the views are {self.tta_views}")
         return head

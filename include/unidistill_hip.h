@@ -1269,6 +1269,31 @@ int ud_tta_merge(const float* const* heads, const long long* strides, float* con
                  const int* num_classes, const int* flips, int V, int B, int T, int H, int W, int no_log,
                  ud_stream_t stream);
 
+/* ---- Rotation / scale / flip test-time augmentation: resampling merge of V views (csrc/tta_merge_affine.hip)
+ * The tables heads / strides / outs / out_strides / num_classes, the view-major rows, the layouts and the output are those
+ * of ud_tta_merge (every stride below 2^31 here); one launch, no workspace, no atomics, bitwise reproducible.
+ *   view_params          HOST double [V*11], 1 <= V <= 16, per view: T (row-major 2x3), Ti (row-major 2x2), s.  Cell (x, y)
+ *                        covers [x, x+1) x [y, y+1) in cell units u; T takes original-frame u to view-frame u
+ *                        (T = C^-1 A_v C with A_v = F S R of the view, C: u -> u * cell + range_min), Ti is the inverse of
+ *                        T's linear part, s > 0 the view's scale.  All finite.  View 0 maps the grid onto itself: s = 1 and
+ *                        per axis (1, 0) or (-1, size) as (linear entry, offset), the cross entries 0.
+ *   cell_ratio           cell_x / cell_y, > 0: metres L^-1_ij = Ti_ij * cell_i / cell_j.
+ * Output pixel p samples view v at q = T (p + 1/2): g = q - 1/2, i0 = floor(g), f = g - i0, neighbours i0 and i0 + 1 per
+ * axis with weights 1 - f and f, all in double.  A view contributes at p only if every neighbour of non-zero weight lies inside
+ * the map; the blended terms of the contributing views are added in the views' order and divided by their number n(p) >= 1.
+ * Terms, per neighbour n, brought into the original frame before the blend: hm: sigmoid(h), the output logit(min(mean, 1)) =
+ * log m - log1p(-m), never NaN; dim: exp(d) / s and the output log(mean), under no_log d / s; height: z / s; iou: as it is;
+ * reg: Ti (n + reg - T's offset) - p, the offset of the predicted centre from the output cell's corner (1 - r for a flip);
+ * vel: L^-1 v; rot (sin, cos): the vector (cos, sin) multiplied by s L^-1, not renormalised.  hm and a logarithmic dim are
+ * carried in double, weights included, and rounded to fp32 once; the other heads are fp32 one operation at a time with
+ * fp32-rounded weights and coefficients (tests/tta_affine_reference.py: merge32 restates the order).
+ * UD_ERR_INVALID_ARG with nothing launched: V outside 1..16, B, T, H, W out of range, a missing table, hm or output pointer,
+ * a negative stride, a non-finite parameter, s <= 0, cell_ratio <= 0, a view 0 that does not map the grid onto itself;
+ * UD_ERR_UNSUPPORTED: a stride >= 2^31, more than 256 channels in all, or B*H*W*channels >= 2^31. */
+int ud_tta_merge_affine(const float* const* heads, const long long* strides, float* const* outs,
+                        const long long* out_strides, const int* num_classes, const double* view_params, double cell_ratio,
+                        int V, int B, int T, int H, int W, int no_log, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
