@@ -605,6 +605,24 @@ class CenterHead(nn.Module):
     # tta.flip_views and hands the merged maps of B samples to the proposal layer.  None: forward is unchanged.
     # Views (rot_deg, scale, flip_dx, flip_dy), e.g. tta.views(rotations=(0, 7.5, -7.5)), are merged by resampling.
     tta_views = None
+    # How the views are combined.  "maps": the merge above.  "boxes": the proposal layer runs on the V * B maps as they are and
+    # the decoded boxes of the views are fused per sample (ops/box_fusion.py): no resampling onto one grid, and
+    # flips need no symmetric range, since boxes carry metric coordinates.  tta_box_iou_threshold None: the proposal layer's
+    # test NMS threshold, so the output density matches the single-view contract.
+    tta_level = "maps"
+    tta_box_iou_threshold = None
+    tta_box_max_out = 500
+
+    def _fuse_view_boxes(self, ret):
+        from ..ops import box_fusion, tta
+        prop = self.proposal_layer
+        views = tta.resolve_views(self.tta_views)
+        rois, scores, labels, num = prop.padded_boxes(ret)
+        thr = prop.nms_iou_threshold_test if self.tta_box_iou_threshold is None else self.tta_box_iou_threshold
+        out = box_fusion.fuse_padded(rois, scores, labels, num, len(views), views=views, iou_threshold=thr,
+                                     max_out=self.tta_box_max_out)
+        return {"pred_dicts": box_fusion.pred_dicts_of(*out),          # the one host read: the fused counts
+                "rois": out[0], "roi_scores": out[1], "roi_labels": out[2], "has_class_labels": True}
 
     def __init__(self, dataset_name, tasks, target_assigner, proposal_layer, input_channels,
                  grid_size, point_cloud_range, code_weights, loc_weight, share_conv_channel,
@@ -666,6 +684,8 @@ class CenterHead(nn.Module):
             return ret
         if self.proposal_layer is None:
             return ret
+        if self.tta_views is not None and self.tta_level == "boxes":
+            return self._fuse_view_boxes(ret)
         if self.tta_views is not None:
             # the batch holds the views of B samples, view-major (ops/tta.py): one kernel un-flips and averages the maps (a
             # list of pure flips, after check_symmetric_range), or -- rotation / scale views -- resamples them onto the

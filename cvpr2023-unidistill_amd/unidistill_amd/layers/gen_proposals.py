@@ -119,14 +119,20 @@ class CenterPointGenProposals(nn.Module):
                 for b, n in enumerate(counts)]
 
     @torch.no_grad()
-    def generate_predicted_boxes(self, forward_ret_dict, data_dict):
+    def padded_boxes(self, forward_ret_dict):
+        """The layer's padded device outputs before the host slices them: (rois f32[B, T * post, box_dim], scores f32[B, T * post],
+        labels i64[B, T * post], num_boxes i32[B]); no host read (ops/box_fusion.py fuses them in place)."""
         pred_dicts = forward_ret_dict["multi_head_features"]
         self._phase()
         offsets, off = [], 0                                   # global labels start at 1 (added on the device)
         for names in self.class_names:
             offsets.append(off)
             off += len(names)
-        rois, scores, labels, counts = self._run(pred_dicts, offsets, self._alphas(len(pred_dicts)))
+        return self._run(pred_dicts, offsets, self._alphas(len(pred_dicts)))
+
+    @torch.no_grad()
+    def generate_predicted_boxes(self, forward_ret_dict, data_dict):
+        rois, scores, labels, counts = self.padded_boxes(forward_ret_dict)
         counts = counts.tolist()                               # the one host read of the layer
         # independent tensors, as the reference returns them (in-place post-processing of pred_boxes must not reach rois)
         data_dict["pred_dicts"] = [{"pred_boxes": rois[b, :n].clone(), "pred_scores": scores[b, :n].clone(),

@@ -443,18 +443,36 @@ class ValidationStep(nn.Module):
     or a list of up to 16 (rot_deg, scale, flip_dx, flip_dy) views (``ops.tta.views``) whose view 0 is a flip or the identity.
     The batch goes through the model once as V * B samples, the head merges the views' maps on the device, and the B merged
     ``pred_dicts`` go to the evaluator.  A list of flips needs a point-cloud range symmetric about 0 on every flipped axis.  With
-    ``depth_metric`` the depth of view 0 is measured, which must be the unflipped one.  ``None``: the step is unchanged."""
+    ``depth_metric`` the depth of view 0 is measured, which must be the unflipped one.  ``None``: the step is unchanged.
 
-    def __init__(self, model, evaluator, weights=None, depth_metric=None, tta=None):
+    ``tta_level``: ``"maps"`` (the merge above) or ``"boxes"``: the proposal layer runs on every view and the decoded boxes of the
+    views are fused per sample on the device (ops/box_fusion.py); flips then need no symmetric range.  ``"boxes"``
+    needs ``tta``.
+
+    ``ensemble``: a list of ``(model, weight)``: the same batch goes through each extra model in eval mode under no_grad (no
+    test-time augmentation there), and its ``pred_dicts`` are fused with the main model's (weight 1) by ``ops.box_fusion.fuse``
+    before the evaluator sees them; ``ensemble_iou_threshold`` None: the main head's test NMS threshold."""
+
+    def __init__(self, model, evaluator, weights=None, depth_metric=None, tta=None, tta_level="maps", ensemble=None,
+                 ensemble_iou_threshold=None):
         super().__init__()
         self.model = model
         self.evaluator = evaluator
         self.weights = weights
         self.depth_metric = depth_metric
         self.tta_views = None
+        if tta_level not in ("maps", "boxes"):
+            raise ValueError(f'tta_level is "maps" or "boxes", got {tta_level!r}')
+        if tta_level == "boxes" and tta is None:
+            raise ValueError('tta_level="boxes" fuses the boxes of the test-time augmentation\'s views, but tta is None')
+        self.tta_level = tta_level
         if tta is not None:
             from .ops import tta as T
             self.tta_views = T.resolve_views(tta)
+        self.ensemble = [(m, float(w)) for m, w in (ensemble or [])]
+        if any(not (w > 0 and w != float("inf")) for _, w in self.ensemble):
+            raise ValueError(f"ensemble weights must be finite and > 0, got {[w for _, w in self.ensemble]}")
+        self.ensemble_iou_threshold = ensemble_iou_threshold
 
     def _check_depth_inputs(self, batch):
         if self.model.camera_encoder is None:
@@ -476,7 +494,8 @@ class ValidationStep(nn.Module):
     def _check_tta(self):
         from .ops import tta as T
         head = self.model.det_head.dense_head
-        if all(len(v) == 2 for v in self.tta_views):        # the flip path; rotation / scale views are resampled on any range
+        # the flip path of the map merge; rotation / scale views are resampled on any range, boxes carry metric coordinates
+        if self.tta_level == "maps" and all(len(v) == 2 for v in self.tta_views):
             T.check_symmetric_range(head.point_cloud_range, self.tta_views)
         if self.depth_metric is not None and not T.is_identity(self.tta_views[0]):
             raise ValueError(f"depth_metric measures view 0 of the test-time augmentation, which must be the unflipped view "
@@ -496,10 +515,10 @@ class ValidationStep(nn.Module):
             points = [p for p in points]
         was_training = self.model.training
         self.model.eval()
-        views_before = None if head is None else head.tta_views
+        views_before, level_before = (None, None) if head is None else (head.tta_views, head.tta_level)
         try:
             if head is not None:
-                head.tta_views = self.tta_views
+                head.tta_views, head.tta_level = self.tta_views, self.tta_level
             weights = contextlib.nullcontext() if self.weights is None else self.weights()
             with weights, torch.no_grad():
                 if self.depth_metric is not None:
@@ -508,10 +527,33 @@ class ValidationStep(nn.Module):
                     out = self.model(points, inputs.get("imgs"), inputs.get("mats_dict"), None)
         finally:
             if head is not None:
-                head.tta_views = views_before
+                head.tta_views, head.tta_level = views_before, level_before
             self.model.train(was_training)
-        self.evaluator.add_batch(sample_ids, out["pred_dicts"], lidar_to_global)
-        return out["pred_dicts"]
+        pred_dicts = out["pred_dicts"]
+        if self.ensemble:
+            pred_dicts = self._fuse_ensemble(batch, pred_dicts)
+        self.evaluator.add_batch(sample_ids, pred_dicts, lidar_to_global)
+        return pred_dicts
+
+    def _fuse_ensemble(self, batch, pred_dicts):
+        from .ops import box_fusion
+        points = batch.get("points")
+        if points is not None and not isinstance(points, (list, tuple)):
+            points = [p for p in points]
+        sources, weights = [pred_dicts], [1.0]
+        for extra, w in self.ensemble:
+            was_training = extra.training
+            extra.eval()
+            try:
+                with torch.no_grad():
+                    sources.append(extra(points, batch.get("imgs"), batch.get("mats_dict"), None)["pred_dicts"])
+            finally:
+                extra.train(was_training)
+            weights.append(w)
+        thr = self.ensemble_iou_threshold
+        if thr is None:
+            thr = self.model.det_head.dense_head.proposal_layer.nms_iou_threshold_test
+        return box_fusion.fuse(sources, weights=weights, iou_threshold=thr)
 
 
 def synthetic_batch(device, batch_size=1, rank=0, ncam=6, sweeps=1, n_boxes=40, max_boxes=50,

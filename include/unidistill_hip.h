@@ -1294,6 +1294,39 @@ int ud_tta_merge_affine(const float* const* heads, const long long* strides, flo
                         const long long* out_strides, const int* num_classes, const double* view_params, double cell_ratio,
                         int V, int B, int T, int H, int W, int no_log, ud_stream_t stream);
 
+/* ---- Box-level fusion (weighted box fusion) of TTA views and ensembles (csrc/box_fusion.hip) -----------------
+ * Fuses the decoded boxes of S sources (views or models) per sample.  Three launches; nothing synchronises with the host, no
+ * allocation, no floating-point atomics, bitwise reproducible.
+ *   rois / scores / labels / num   DEVICE f32[S*B, R, box_dim] / f32[S*B, R] / i64[S*B, R] / i32[S*B]: ud_proposal_layer's padded
+ *                        outputs, read in place; source s of sample b is row s * B + b; rows at or beyond num (clamped to 0..R)
+ *                        are never read.  box_dim 7 or 9: (x, y, z, dx, dy, dz, yaw[, vx, vy]).
+ *   views                HOST double [S*6], per source: rot_deg, scale > 0, flip_dx, flip_dy, sin, cos of the rotation (the
+ *                        caller's: ops.tta._sincos, exact at multiples of 90 degrees; sin^2 + cos^2 = 1 within 1e-12).
+ *   weights              HOST double [S], each > 0.
+ * Un-view (double, from the fp32 inputs; A_v = F S R): (x, y) = R^T F (x', y') / s, z = z' / s, dims = dims' / s, (vx, vy) =
+ * R^T F (vx', vy') / s; yaw = yaw' - rot | -yaw' - rot (flip_dy) | pi - yaw' - rot (flip_dx) | pi + yaw' - rot (both), rot =
+ * rot_deg / 180 * pi.  A box is valid iff every entry and the score are finite, score > score_threshold and 0 <= label <= 65535;
+ * others count nowhere.  Order per sample: (label ascending, score descending, source ascending, row ascending).  Clusters: greedy
+ * NMS within a label on the un-viewed boxes rounded to fp32, ud_boxes_iou_bev's arithmetic with the earlier box first, strict
+ * IoU > iou_threshold; an unsuppressed box is an anchor, a suppressed box joins the first anchor in order that suppresses it,
+ * suppressed boxes suppress nobody.  Fusion in double over the un-viewed values, members in order, anchor first, c_i = w_s(i) *
+ * score_i: centre, dims, velocity = sum c_i v_i / sum c_i; yaw = yaw_a + sum c_i d_i / sum c_i wrapped into [-pi, pi), d_i =
+ * yaw_i - yaw_a wrapped to (-pi, pi] and folded by -+pi into [-pi/2, pi/2]; score = sum c_i / max(sum_i w_s(i), sum_s w_s);
+ * each rounded to fp32 once.
+ * Outputs (DEVICE): out_rois f32[B, max_out, box_dim], out_scores f32[B, max_out], out_labels i64[B, max_out], zero padded, the
+ * clusters by fused fp32 score descending, ties in anchor order, cut at max_out; out_num i32[B]; status i32[B]: 1 for a sample
+ * with more than 16384 valid boxes (possible only when S * R > 16384), which is not fused: its out_num is 0.  Optional (NULL
+ * to skip) out_anchor i32[B, max_out]: s * R + r of each cluster's anchor (-1 in the padding), out_members i32[B, max_out]: its
+ * member count.
+ * UD_ERR_INVALID_ARG with nothing launched: B outside 1..65535, S outside 1..16, R < 1, S * R > 2^24, box_dim not 7 or 9,
+ * max_out < 1, a non-finite iou_threshold, a NaN score_threshold, a non-finite view entry, scale or weight <= 0, a missing
+ * pointer; UD_ERR_WORKSPACE: less than ud_box_fusion_workspace_bytes(B, S, R) (0 for sizes out of range). */
+size_t ud_box_fusion_workspace_bytes(int B, int S, int R);
+int ud_box_fusion(const float* rois, const float* scores, const long long* labels, const int* num, int B, int S, int R,
+                  int box_dim, const double* views, const double* weights, float iou_threshold, float score_threshold,
+                  int max_out, float* out_rois, float* out_scores, long long* out_labels, int* out_num, int* status,
+                  int* out_anchor, int* out_members, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
