@@ -58,7 +58,42 @@ struct W4Geom {
   // instead of 2, a 552-unit layer 2.4 instead of 3.
   int n_dp, n_units, sk_len;
   float* partial;                   // [2 * gridDim.x][512 rows][64] fp32 partial tiles (before bias / BatchNorm / ReLU)
+  // ACT kernels (ud_conv3x3_wino4_units_nhwc_f32): the launch walks the *act_count tile blocks act_list names (ascending) instead
+  // of all B * bx * by.  n_units is the dense count (it tells the output-channel blocks); every workgroup derives the schedule of
+  // the listed units from the count with w4_sched_core, the rule of the dense launches (sk_allow: stream-K tail permitted).
+  const int* act_list;
+  const int* act_count;
+  int sk_allow;
 };
+
+struct W4Sched {
+  int grid, n_dp, sk_len;
+};
+// data-parallel rounds + a stream-K tail where that beats one more (mostly idle) round; a piece costs ~8 stages of prologue + epilogue
+__host__ __device__ inline W4Sched w4_sched_core(long long units, int gmax, int nchunks, bool allow_tail) {
+  const int G = (int)(units < gmax ? units : gmax);
+  W4Sched sc{G, (int)units, 0};
+  if (G <= 0) return sc;
+  const int r = (int)(units % G);
+  if (r == 0 || !allow_tail) return sc;
+  int len = (int)(((long long)r * nchunks + G - 1) / G);
+  len += len & 1;
+  if (len + 16 >= (nchunks + 8) * 9 / 10) return sc;
+  sc.n_dp = (int)(units - r), sc.sk_len = len;
+  return sc;
+}
+// the schedule an ACT kernel walks: (workgroups that take part, n_dp, n_units, sk_len) of the listed blocks
+struct W4Act {
+  int nblocks, grid, n_dp, n_units, sk_len;
+};
+__device__ __forceinline__ W4Act w4_act_schedule(const W4Geom& gm, int nblocks, int nchunks, int gmax) {
+  W4Act a;
+  a.nblocks = min(max(*gm.act_count, 0), nblocks);
+  a.n_units = a.nblocks * (gm.n_units / nblocks);
+  const W4Sched sc = w4_sched_core(a.n_units, gmax, nchunks, gm.sk_allow != 0);
+  a.grid = sc.grid, a.n_dp = sc.n_dp, a.sk_len = sc.sk_len > 0 ? sc.sk_len : 2;
+  return a;
+}
 struct W4Ep {
   const float* bias;
   const float* scale;               // folded eval-mode BatchNorm: v * scale + shift after the bias (both or neither)
@@ -264,7 +299,7 @@ __host__ __device__ constexpr int w4_wait(int fq) {   // LDS operations issued a
   return (fq > 0 ? kStepOps[fq - 1] : 0) + 2 + kStepOps[fq];
 }
 
-template <int TWB, int THB>
+template <int TWB, int THB, bool ACT = false>
 __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restrict__ x, const float* __restrict__ U,
                                                            float* __restrict__ y, W4Geom gm, W4Ep ep) {
   constexpr int PW = 4 * TWB + 2, PH = 4 * THB + 2;
@@ -286,6 +321,13 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restri
   const int wq = wave & 3, wh = wave >> 2;
   const int nblocks = gm.B * gm.bx * gm.by;
   const int nchunks = gm.Cin / kKC;                    // even (Cin % 8 == 0)
+  // the blocks and the schedule walked: the launch's own, or (ACT) those of the listed blocks
+  int s_nblocks = nblocks, s_grid = gridDim.x, s_ndp = gm.n_dp, s_nunits = gm.n_units, s_sklen = gm.sk_len;
+  if constexpr (ACT) {
+    const W4Act a = w4_act_schedule(gm, nblocks, nchunks, gridDim.x);
+    s_nblocks = a.nblocks, s_grid = a.grid, s_ndp = a.n_dp, s_nunits = a.n_units, s_sklen = a.sk_len;
+    if ((int)blockIdx.x >= s_grid) return;
+  }
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)((unsigned)gm.B * gm.H * gm.W * gm.Cin * 4u), 0x00020000);
   const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)U, 0, (int)gm.u_bytes, 0x00020000);
 
@@ -297,13 +339,14 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restri
   auto setup = [&](int unit_, int c0, int c1) {
     unit = unit_;
     nst = c1 - c0;
-    cbi = unit / nblocks;
-    const int ru_ = unit - cbi * nblocks;
+    cbi = unit / s_nblocks;
+    const int ru_ = unit - cbi * s_nblocks;
     int blk;
     {   // consecutive items go round the 8 XCDs: XCD k walks its own contiguous range of tile blocks (shared halos stay in its L2)
-      const int base = nblocks >> 3, extra = nblocks & 7, k = ru_ & 7;
+      const int base = s_nblocks >> 3, extra = s_nblocks & 7, k = ru_ & 7;
       blk = k * base + min(k, extra) + (ru_ >> 3);
     }
+    if constexpr (ACT) blk = min(max(gm.act_list[blk], 0), nblocks - 1);
     blk_lin = blk;
     b = blk / (gm.bx * gm.by);
     blk -= b * gm.bx * gm.by;
@@ -527,13 +570,13 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restri
   };
 
   // ---- the workgroup's pieces: whole units first (data parallel), then its stream-K range
-  const int G = gridDim.x;
+  const int G = s_grid;
   int dp_next = blockIdx.x;                                   // next data-parallel unit
-  int sk_lo = gm.n_dp * nchunks + blockIdx.x * gm.sk_len;     // rest of this workgroup's stream-K range, in global stage numbers
-  const int sk_hi = min(sk_lo + gm.sk_len, gm.n_units * nchunks);
+  int sk_lo = s_ndp * nchunks + blockIdx.x * s_sklen;         // rest of this workgroup's stream-K range, in global stage numbers
+  const int sk_hi = min(sk_lo + s_sklen, s_nunits * nchunks);
   int p_unit, p_c0, p_c1, p_slot;                             // piece: unit, stages [c0, c1), partial slot (-1: the whole unit)
   auto next_piece = [&]() -> bool {
-    if (dp_next < gm.n_dp) {
+    if (dp_next < s_ndp) {
       p_unit = dp_next, p_c0 = 0, p_c1 = nchunks, p_slot = -1;
       dp_next += G;
       return true;
@@ -542,7 +585,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restri
     p_unit = sk_lo / nchunks;
     p_c0 = sk_lo - p_unit * nchunks;
     p_c1 = min(nchunks, p_c0 + sk_hi - sk_lo);
-    const bool first = sk_lo == gm.n_dp * nchunks + (int)blockIdx.x * gm.sk_len;
+    const bool first = sk_lo == s_ndp * nchunks + (int)blockIdx.x * s_sklen;
     p_slot = (p_c0 == 0 && p_c1 == nchunks) ? -1 : 2 * blockIdx.x + (first ? 0 : 1);
     sk_lo += p_c1 - p_c0;
     return true;
@@ -643,22 +686,30 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4_f32(const float* __restri
 // workgroups per stream-K unit (one per staging pass = 16 of its 32 tiles), eight independent rows in flight per thread; a unit
 // that one workgroup covered completely was stored by k_conv3x3_wino4_f32 itself.  BatchNorm partial sums of a cut unit go to
 // the extra rows nblocks + 2 * (unit - n_dp) + pass (zeroed by the launcher); its own row is cleared here.
-template <int TWB, int THB>
-__global__ __launch_bounds__(512) void k_wino4_fixup(float* __restrict__ y, W4Geom gm, W4Ep ep) {
+// ACT: launched with the most workgroups the schedule of any count can need; those past the listed units' stream-K tail return.
+template <int TWB, int THB, bool ACT = false>
+__global__ __launch_bounds__(512) void k_wino4_fixup(float* __restrict__ y, W4Geom gm, W4Ep ep, int gmax) {
   __shared__ float red[32 * 64 * 2];
   const int tid = threadIdx.x;
   const int nblocks = gm.B * gm.bx * gm.by, nchunks = gm.Cin / kKC;
-  const int u = gm.n_dp + (blockIdx.x >> 1), pass = blockIdx.x & 1;
-  const int base = gm.n_dp * nchunks;
+  int s_nblocks = nblocks, s_ndp = gm.n_dp, s_sklen = gm.sk_len;
+  if constexpr (ACT) {
+    const W4Act a = w4_act_schedule(gm, nblocks, nchunks, gmax);
+    s_nblocks = a.nblocks, s_ndp = a.n_dp, s_sklen = a.sk_len;
+    if (s_ndp + (int)(blockIdx.x >> 1) >= a.n_units) return;
+  }
+  const int u = s_ndp + (blockIdx.x >> 1), pass = blockIdx.x & 1;
+  const int base = s_ndp * nchunks;
   const int a = u * nchunks - base, e = a + nchunks - 1;              // the unit's stages within the stream-K sequence
-  const int j0 = a / gm.sk_len, j1 = e / gm.sk_len;
+  const int j0 = a / s_sklen, j1 = e / s_sklen;
   if (j0 == j1) return;
-  const int cbi = u / nblocks, ru = u - cbi * nblocks;
+  const int cbi = u / s_nblocks, ru = u - cbi * s_nblocks;
   int blk;
   {
-    const int bs = nblocks >> 3, extra = nblocks & 7, k = ru & 7;
+    const int bs = s_nblocks >> 3, extra = s_nblocks & 7, k = ru & 7;
     blk = k * bs + min(k, extra) + (ru >> 3);
   }
+  if constexpr (ACT) blk = min(max(gm.act_list[blk], 0), nblocks - 1);
   const int blk_lin = blk;
   const int b = blk / (gm.bx * gm.by);
   blk -= b * gm.bx * gm.by;
@@ -668,7 +719,7 @@ __global__ __launch_bounds__(512) void k_wino4_fixup(float* __restrict__ y, W4Ge
   for (int k = 0; k < 8; ++k) v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 1
   for (int j = j0; j <= j1; ++j) {
-    const int first_unit = (base + j * gm.sk_len) / nchunks;     // the first unit workgroup j touched
+    const int first_unit = (base + j * s_sklen) / nchunks;       // the first unit workgroup j touched
     const int slot = 2 * j + (first_unit == u ? 0 : 1);
     const float* src = gm.partial + ((size_t)slot * 512 + pass * 256 + (tid >> 4)) * 64 + tail.c4;
 #pragma unroll
@@ -680,7 +731,7 @@ __global__ __launch_bounds__(512) void k_wino4_fixup(float* __restrict__ y, W4Ge
 #pragma unroll
   for (int k = 0; k < 8; ++k) tail.store(y, pass, (tid >> 4) + 32 * k, v[k]);
   if (ep.stats) {
-    tail.reduce_stats(red, nblocks + 2 * (u - gm.n_dp) + pass);
+    tail.reduce_stats(red, nblocks + 2 * (u - s_ndp) + pass);
     if (pass == 0 && tid < 64 && tail.n0 + tid < gm.Cout)
       ep.stats[((size_t)blk_lin * gm.Cout + tail.n0 + tid) * 2] = ep.stats[((size_t)blk_lin * gm.Cout + tail.n0 + tid) * 2 + 1] = 0.f;
   }
@@ -713,27 +764,22 @@ W4Plan w4_plan(int H, int W) {
 namespace {
 std::atomic<int> g_sk_mode{-1};        // ud_conv3x3_wino4_stream_k: -1 default (UD_WINO4_SK or 2), 0 never, 1 deep reductions only, 2 whenever a tail exists and beats a whole round
 constexpr int kGrid = 256;             // persistent workgroups: one per CU
-struct W4Sched {
-  int grid, n_dp, sk_len;
-};
-// data-parallel rounds + a stream-K tail where that beats one more (mostly idle) round; a piece costs ~8 stages of prologue + epilogue
-W4Sched w4_schedule(long long units, int nchunks, bool have_ws) {
+// whether the stream-K tail is permitted at all (workspace, mode); w4_sched_core decides whether it pays
+bool w4_tail_allowed(int nchunks, bool have_ws) {
   static const int env_mode = getenv("UD_WINO4_SK") ? atoi(getenv("UD_WINO4_SK")) : 2;
   const int forced = g_sk_mode.load(std::memory_order_relaxed);
   const int mode = forced >= 0 ? forced : env_mode;
+  return have_ws && mode && !(nchunks < 64 && mode < 2);
+}
+int w4_persist() {
   static const int persist = getenv("UD_WINO4_GRID") ? atoi(getenv("UD_WINO4_GRID")) : kGrid;
-  const int G = (int)std::min<long long>(units, persist);
-  const int r = (int)(units % G);
-  W4Sched sc{G, (int)units, 0};
+  return persist;
+}
+W4Sched w4_schedule(long long units, int nchunks, bool have_ws) {
   // measured (tools/time_wino4.py, fix-up with two workgroups per unit): the tail pays on every layer shape of the step -- 512 -> 64
   // @180^2 407 -> 262 us, 2688 -> 64 2121 -> 1236 us, 128 -> 128 @180^2 179 -> 161 us, 128 -> 128 @32 x 88 x 24 113 -> 88 us
   // (mode 1 keeps it to Cin >= 256)
-  if (r == 0 || !have_ws || !mode || (nchunks < 64 && mode < 2)) return sc;
-  int len = (int)(((long long)r * nchunks + G - 1) / G);
-  len += len & 1;
-  if (len + 16 >= (nchunks + 8) * 9 / 10) return sc;
-  sc.n_dp = (int)(units - r), sc.sk_len = len;
-  return sc;
+  return w4_sched_core(units, w4_persist(), nchunks, w4_tail_allowed(nchunks, have_ws));
 }
 }  // namespace
 
@@ -779,10 +825,10 @@ extern "C" size_t ud_conv3x3_wino4_f32_workspace_bytes(int B, int H, int W, int 
 // y = conv3x3(x) (+ bias) (* scale + shift: a folded eval-mode BatchNorm) (+ residual) (ReLU if flags & 1) with U from
 // ud_conv3x3_wino4_f32_weights(N = Cout, C = Cin); partial != nullptr: also the per-workgroup BatchNorm partial sums
 // ([*slices][Cout][2], same contract as ud_conv3x3_bnstats_nhwc_f32).
-extern "C" int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* y, int B, int H, int W, int Cin, int Cout,
-                                         const float* bias, const float* scale, const float* shift, const float* residual,
-                                         int flags, float* partial, size_t partial_bytes, int* slices, void* workspace,
-                                         size_t workspace_bytes, ud_stream_t stream_) {
+static int w4_forward(const float* x, const float* U, float* y, int B, int H, int W, int Cin, int Cout, const float* bias,
+                      const float* scale, const float* shift, const float* residual, int flags, float* partial,
+                      size_t partial_bytes, int* slices, const int* act_list, const int* act_count, void* workspace,
+                      size_t workspace_bytes, ud_stream_t stream_) {
   if (!x || !U || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return UD_ERR_INVALID_ARG;
   if ((scale == nullptr) != (shift == nullptr)) return UD_ERR_INVALID_ARG;
   if (Cin % (2 * kKC) != 0 || Cout % 4 != 0) return UD_ERR_UNSUPPORTED;     // stages come in pairs (8-channel patch fetches)
@@ -796,7 +842,7 @@ extern "C" int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* 
   const bool have_ws = workspace && workspace_bytes >= ud_conv3x3_wino4_f32_workspace_bytes(B, H, W, Cin, Cout);
   const W4Sched sc = w4_schedule(units, Cin / kKC, have_ws);
   W4Geom gm{B, H, W, Cin, Cout, p.bx, p.by, (unsigned)ud_conv3x3_wino4_f32_weight_bytes(Cin, Cout), sc.n_dp, (int)units,
-            sc.sk_len > 0 ? sc.sk_len : 2, (float*)workspace};
+            sc.sk_len > 0 ? sc.sk_len : 2, (float*)workspace, act_list, act_count, w4_tail_allowed(Cin / kKC, have_ws) ? 1 : 0};
   W4Ep ep{bias, scale, shift, residual, flags & 1, partial};
   if (partial) {
     const size_t rows = (size_t)nblocks + 2 * (size_t)(units - sc.n_dp);
@@ -807,19 +853,27 @@ extern "C" int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* 
   }
   static UdDeviceOnce attr_set;
   if (const unsigned long long attr_set_bit = attr_set.pending()) {
-#define UD_W4_ATTR(A, Bq) \
-  UD_HIP_TRY(hipFuncSetAttribute((const void*)k_conv3x3_wino4_f32<A, Bq>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem))
+#define UD_W4_ATTR(...) \
+  UD_HIP_TRY(hipFuncSetAttribute((const void*)k_conv3x3_wino4_f32<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem))
     UD_W4_ATTR(8, 4); UD_W4_ATTR(4, 8); UD_W4_ATTR(16, 2);
+    UD_W4_ATTR(8, 4, true); UD_W4_ATTR(4, 8, true); UD_W4_ATTR(16, 2, true);
 #undef UD_W4_ATTR
     attr_set.mark(attr_set_bit);
   }
-  UdProfScope prof("conv2d.k_conv3x3_wino4_f32", stream);
+  UdProfScope prof(act_list ? "conv2d.k_conv3x3_wino4_f32_units" : "conv2d.k_conv3x3_wino4_f32", stream);
   const dim3 grid((unsigned)sc.grid);
   const int n_sk = (int)units - sc.n_dp;
-#define UD_W4_LAUNCH(A, Bq)                                                                    \
-  do {                                                                                         \
-    k_conv3x3_wino4_f32<A, Bq><<<grid, 512, kSmem, stream>>>(x, U, y, gm, ep);                 \
-    if (n_sk > 0) k_wino4_fixup<A, Bq><<<2 * n_sk, 512, 0, stream>>>(y, gm, ep);               \
+  // a list: the dense launch's grid; the fix-up gets the workgroups the longest stream-K tail of any count needs (< grid units)
+  const int n_fix = w4_tail_allowed(Cin / kKC, have_ws) ? sc.grid - 1 : 0;
+#define UD_W4_LAUNCH(A, Bq)                                                                                     \
+  do {                                                                                                          \
+    if (act_list) {                                                                                             \
+      k_conv3x3_wino4_f32<A, Bq, true><<<grid, 512, kSmem, stream>>>(x, U, y, gm, ep);                          \
+      if (n_fix > 0) k_wino4_fixup<A, Bq, true><<<2 * n_fix, 512, 0, stream>>>(y, gm, ep, sc.grid);             \
+    } else {                                                                                                    \
+      k_conv3x3_wino4_f32<A, Bq><<<grid, 512, kSmem, stream>>>(x, U, y, gm, ep);                                \
+      if (n_sk > 0) k_wino4_fixup<A, Bq><<<2 * n_sk, 512, 0, stream>>>(y, gm, ep, sc.grid);                     \
+    }                                                                                                           \
   } while (0)
   if (p.twb == 8) UD_W4_LAUNCH(8, 4);
   else if (p.twb == 4) UD_W4_LAUNCH(4, 8);
@@ -827,4 +881,28 @@ extern "C" int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* 
 #undef UD_W4_LAUNCH
   UD_LAUNCH_CHECK();
   return UD_OK;
+}
+
+extern "C" int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* y, int B, int H, int W, int Cin, int Cout,
+                                         const float* bias, const float* scale, const float* shift, const float* residual,
+                                         int flags, float* partial, size_t partial_bytes, int* slices, void* workspace,
+                                         size_t workspace_bytes, ud_stream_t stream_) {
+  return w4_forward(x, U, y, B, H, W, Cin, Cout, bias, scale, shift, residual, flags, partial, partial_bytes, slices, nullptr,
+                    nullptr, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ud_conv3x3_wino4_f32_block_shape(int H, int W) {
+  if (H <= 0 || W <= 0) return 0;
+  const W4Plan p = w4_plan(H, W);
+  return (p.twb << 8) | p.thb;
+}
+
+// the forward launch over the listed tile blocks only (see W4Geom): blocks that are not listed keep what y held
+extern "C" int ud_conv3x3_wino4_units_nhwc_f32(const float* x, const float* U, float* y, int B, int H, int W, int Cin, int Cout,
+                                               const float* bias, const float* scale, const float* shift, const float* residual,
+                                               int flags, const int* unit_list, const int* unit_count, void* workspace,
+                                               size_t workspace_bytes, ud_stream_t stream_) {
+  if (!unit_list || !unit_count) return UD_ERR_INVALID_ARG;
+  return w4_forward(x, U, y, B, H, W, Cin, Cout, bias, scale, shift, residual, flags, nullptr, 0, nullptr, unit_list, unit_count,
+                    workspace, workspace_bytes, stream_);
 }

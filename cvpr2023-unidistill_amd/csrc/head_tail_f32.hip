@@ -54,11 +54,16 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b, float ac
 // thread per pixel; lane = channel with nine row reads per pixel and shuffle reductions; lane = channel with a register
 // halo and 64-lane DPP reductions -- instruction-bound: 140 instructions per pixel.)
 __device__ __attribute__((aligned(16))) unsigned int g_zero_f4[4];
-template <int KM, bool BN>
+// SITES (the frozen distillation teacher, whose only consumer weights every site by `mask`): z = the same sums where mask > 0 and
+// exactly 0 elsewhere.  site_rows[strip] = (first, end) rows of the strip's sites (csrc/head_sites.hip): the workgroup walks
+// those rows only and zero-fills the rest of its strip; a strip without sites reads nothing.  The first convolution skipped the
+// blocks no site reads, so sums off the sites may meet stale memory -- they are computed and dropped by a select.
+template <int KM, bool BN, bool SITES = false>
 __global__ __launch_bounds__(256) void k_gtail_fwd(const float* __restrict__ a, const float* __restrict__ w,
                                                    const float* __restrict__ bias, float* __restrict__ z, GTail t,
                                                    int strip_rows, int strips, const float* __restrict__ bn_scale,
-                                                   const float* __restrict__ bn_shift) {
+                                                   const float* __restrict__ bn_shift, const float* __restrict__ mask,
+                                                   const int* __restrict__ site_rows) {
   // groups vary fastest over the grid: the workgroups running together consume whole pixel rows
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // A workgroup walks a 16-pixel-wide strip of `strip_rows` rows (a multiple of kTH): the window keeps sliding across the
@@ -70,10 +75,27 @@ __global__ __launch_bounds__(256) void k_gtail_fwd(const float* __restrict__ a, 
   const int tx = bidx % t.tiles_x;
   bidx /= t.tiles_x;
   const int strip = bidx % strips, b = bidx / strips;
-  const int tx0 = tx * kTW, ty0 = strip * strip_rows;
-  const int y_end = min(t.H, ty0 + strip_rows);
+  const int tx0 = tx * kTW;
+  int ty0 = strip * strip_rows;
+  int y_end = min(t.H, ty0 + strip_rows);
   const int Ct = t.G * kHC, Zt = t.G * KM;
   const int ps = lane >> 4, cq = lane & 15;
+  if constexpr (SITES) {
+    const int s_top = ty0, s_end = y_end;
+    const int lo = site_rows[2 * blockIdx.y], hi = site_rows[2 * blockIdx.y + 1];
+    const bool on = hi > lo;
+    ty0 = on ? min(max(lo, s_top), s_end) : s_end;
+    y_end = on ? max(min(hi, s_end), ty0) : s_end;
+    const int gxz = tx0 + 4 * wave + ps;
+    if (gxz < t.W)
+      for (int gy = s_top + cq; gy < s_end; gy += 16)
+        if (gy < ty0 || gy >= y_end) {
+          float* q = z + ((size_t)(b * t.H + gy) * t.W + gxz) * Zt + g * KM;
+#pragma unroll
+          for (int k = 0; k < KM; ++k) q[k] = 0.f;
+        }
+    if (ty0 >= y_end) return;
+  }
   float4 wr[KM][9];
 #pragma unroll
   for (int k = 0; k < KM; ++k)
@@ -141,11 +163,17 @@ __global__ __launch_bounds__(256) void k_gtail_fwd(const float* __restrict__ a, 
   for (int k = 0; k < KM; ++k) bv[k] = bias ? bias[g * KM + k] : 0.f;
   float* zo = z + ((size_t)(b * t.H + ty0) * t.W + gx) * Zt + g * KM;      // this lane's output pixel, stepped per row
   const size_t zstride = (size_t)t.W * Zt;
+  const float* mp = SITES ? mask + ((size_t)b * t.H + ty0) * t.W + gx : nullptr;      // this lane's site weight, stepped per row
   for (int y0 = ty0; y0 < y_end; y0 += kTH) {
 #pragma unroll
     for (int y = 0; y < kTH; ++y) {
       const int gy = y0 + y;
       load_next(rows[y + 2 + PD]);
+      float mk = 0.f;
+      if constexpr (SITES) {
+        if (cq == 15 && gy < y_end && gx < t.W) mk = *mp;
+        mp += t.W;
+      }
       if constexpr (BN) bn_row(rows[y + 2], gy + 1);
       float acc[KM];
 #pragma unroll
@@ -157,7 +185,7 @@ __global__ __launch_bounds__(256) void k_gtail_fwd(const float* __restrict__ a, 
       }
       if (cq == 15 && gy < y_end && gx < t.W) {
 #pragma unroll
-        for (int k = 0; k < KM; ++k) zo[k] = acc[k] + bv[k];
+        for (int k = 0; k < KM; ++k) zo[k] = (!SITES || mk > 0.f) ? acc[k] + bv[k] : 0.f;
       }
       zo += zstride;
     }
@@ -511,7 +539,7 @@ static int gtail_fwd_impl(const float* a, const float* bn_scale, const float* bn
   const dim3 grid(G, B * t.tiles_x * strips);
   gtail_with_km(KM, [&](auto km) {
     const auto k = bn_scale ? k_gtail_fwd<km(), true> : k_gtail_fwd<km(), false>;
-    k<<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift);
+    k<<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift, nullptr, nullptr);
   });
   UD_LAUNCH_CHECK();
   return UD_OK;
@@ -528,6 +556,29 @@ extern "C" int ud_head_tail_f32_bn_fwd(const float* a, const float* bn_scale, co
                                        const float* bias, float* z, int B, int H, int W, int G, int KM, ud_stream_t stream_) {
   if (!bn_scale || !bn_shift) return UD_ERR_INVALID_ARG;
   return gtail_fwd_impl(a, bn_scale, bn_shift, w, bias, z, B, H, W, G, KM, stream_);
+}
+
+extern "C" int ud_head_tail_f32_strip_rows(int B, int H, int W, int G, int KM) {
+  if (!gtail_ok(B, H, W, G, KM)) return 0;
+  return gtail_strip_rows(GTail{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)});
+}
+
+// ud_head_tail_f32_bn_fwd with the dense launch's grid: z = its result where mask > 0, exactly 0 elsewhere; strips without a site
+// (site_rows from ud_head_sites_build, strip size kTW x ud_head_tail_f32_strip_rows) only zero their outputs
+extern "C" int ud_head_tail_f32_bn_fwd_sites(const float* a, const float* bn_scale, const float* bn_shift, const float* w,
+                                             const float* bias, float* z, int B, int H, int W, int G, int KM, const float* mask,
+                                             const int* site_rows, ud_stream_t stream_) {
+  if (!a || !w || !z || !bn_scale || !bn_shift || !mask || !site_rows || !gtail_ok(B, H, W, G, KM)) return UD_ERR_INVALID_ARG;
+  GTail t{B, H, W, G, KM, ud_div_up(W, kTW), ud_div_up(H, kTH)};
+  hipStream_t stream = (hipStream_t)stream_;
+  UdProfScope prof("head_tail.k_gtail_fwd_sites", stream);
+  const int strip_rows = gtail_strip_rows(t), strips = ud_div_up(H, strip_rows);
+  const dim3 grid(G, B * t.tiles_x * strips);
+  gtail_with_km(KM, [&](auto km) {
+    k_gtail_fwd<km(), true, true><<<grid, 256, 0, stream>>>(a, w, bias, z, t, strip_rows, strips, bn_scale, bn_shift, mask, site_rows);
+  });
+  UD_LAUNCH_CHECK();
+  return UD_OK;
 }
 
 extern "C" int ud_head_tail_f32_dgrad(const float* dz, const float* w, float* da, int B, int H, int W, int G,

@@ -30,7 +30,8 @@ _SCALARS = {
 _TYPED_POINTERS = {"ud_prof_read": {"double *": ctypes.POINTER(ctypes.c_double), "int *": ctypes.POINTER(c_int)}}
 # Entry points whose int result is a value (a count, a flag, ud_jpeg_parse's positive codes), not a UD_ERR_* status.
 VALUE_RETURNS = ("ud_abi_version", "ud_voxelize_capacity", "ud_optim_chunk_elems", "ud_conv1x1_f32_persistent_enabled",
-                 "ud_conv3x3_wino4_f32_blocks", "ud_conv3x3_wino_f32_blocks", "ud_jpeg_parse")
+                 "ud_conv3x3_wino4_f32_blocks", "ud_conv3x3_wino_f32_blocks", "ud_jpeg_parse",
+                 "ud_conv3x3_wino4_f32_block_shape", "ud_head_tail_f32_strip_rows")
 
 _PROTO = re.compile(r"([^;{}()]*?)\b(ud_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
 

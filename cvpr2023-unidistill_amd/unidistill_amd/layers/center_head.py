@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _lib
 from ..dist import reduce_mean, reduce_mean_many
-from ..ops import bn_act as hipbn, conv2d as hipconv, conv2d_f32 as hipconv32, det_loss as hiploss, head_tail, \
+from ..ops import bn_act as hipbn, conv2d as hipconv, conv2d_f32 as hipconv32, det_loss as hiploss, head_sites, head_tail, \
     head_tail_f32
 from .dense import Conv2d, FusedSequential
 
@@ -460,9 +460,29 @@ class PackedSepHeads(nn.Module):
     def __len__(self):
         return self.num_tasks
 
-    def forward(self, x):
-        """-> list (per task) of {head: [B, k, H, W]} like [SepHead(x) for each task]."""
+    def _site_path(self, x, site_mask):
+        """The restricted pass is exact for a frozen, eval-mode, fp32 head only: eval-mode BatchNorm is a per-channel affine, so
+        no batch statistic couples the sites (a training-mode BatchNorm needs every pixel)."""
+        return (site_mask is not None and not self.training and not torch.is_grad_enabled() and self.k == 3
+                and self.fused_bn_tail_f32 and Conv2d.hip_enabled and Conv2d.hip_fp32 and x.is_cuda and x.dtype == torch.float32
+                and not torch.is_autocast_enabled("cuda") and hipconv32.units_supported(x, self.c1_weight)
+                and self.head_conv == 64 and 1 <= self.kmax <= 4
+                and tuple(site_mask.shape[-2:]) == tuple(x.shape[-2:]))
+
+    def forward(self, x, site_mask=None):
+        """-> list (per task) of {head: [B, k, H, W]} like [SepHead(x) for each task].
+
+        site_mask f32 [B, (1,) H, W]: the caller reads the outputs weighted by this mask only (the frozen distillation teacher:
+        ResponseDistillLoss).  Where the configuration allows (_site_path) both convolutions then run on the work units that hold a
+        site with mask > 0 (ops/head_sites.py): the outputs are the dense pass's there and exactly 0 elsewhere."""
         pad = self.k // 2
+        if self._site_path(x, site_mask):
+            G = len(self.layout)
+            sites = head_sites.build(site_mask, G, self.kmax)
+            y = hipconv32.conv3x3_units(x, self.c1_weight, self.c1_bias, sites.conv_units)
+            return self._split(head_tail_f32.bn_relu_group_tail_sites(
+                y, self.bn_weight, self.bn_bias, self.bn_running_mean, self.bn_running_var, self.bn_eps, self.c2_weight,
+                self.c2_bias, G, self.kmax, sites))
         if Conv2d.hip_enabled and self.k == 3 and x.is_cuda and x.dtype == torch.bfloat16 \
                 and hipconv.supported(x, self.c1_weight):
             y = hipconv.conv3x3(x, self.c1_weight, self.c1_bias)      # 64 -> 42*64 on the MFMA kernel
@@ -666,17 +686,22 @@ class CenterHead(nn.Module):
     def assign_targets(self, gt_boxes):
         return self.target_assigner.assign_targets(gt_boxes)
 
-    def forward(self, spatial_features_2d, gt_boxes=None, targets=None):
+    def forward(self, spatial_features_2d, gt_boxes=None, targets=None, response_mask=None):
+        """response_mask: the Gaussian box mask of ResponseDistillLoss, from the distillation step for its frozen teacher -- the
+        one consumer of a distill head's maps reads them weighted by it, so the packed heads may skip the rest (shared_conv stays
+        dense).  Ignored unless self.distill is set and grad mode is off."""
         x = self.shared_conv(spatial_features_2d)
         if self.upsample_for_pedestrian:
             x = self.upsample_conv(x)
         if isinstance(self.tasks, PackedSepHeads):
-            ret = {"multi_head_features": self.tasks(x)}
+            sites = response_mask if (self.distill and not torch.is_grad_enabled()) else None
+            ret = {"multi_head_features": self.tasks(x, site_mask=sites)}
         else:
             ret = {"multi_head_features": [task(x) for task in self.tasks]}
         if self.training or self.distill:
             # The reference also assigns targets for the frozen distillation teacher
-            # (center_head.py:137); they are never read, so the teacher skips the work here.
+            # (center_head.py:137); they are never read, so the teacher skips the work here.  (Likewise its head maps off the
+            # response mask, which no loss reads: see response_mask above.)
             if targets is not None:
                 ret.update(targets)
             elif gt_boxes is not None and not self.distill:

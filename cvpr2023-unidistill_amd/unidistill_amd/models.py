@@ -65,8 +65,9 @@ class DetHead(nn.Module):
             init_bias=cfg["init_bias"], focal_alpha=cfg["focal_alpha"], focal_gamma=cfg["focal_gamma"],
             voxel_size_xy=cfg["voxel_size"][0:2], iou_mode=cfg.get("iou_mode", "reference"))
 
-    def forward(self, x, gt_boxes, targets=None):
-        ret = self.dense_head(x, gt_boxes, targets=targets)
+    def forward(self, x, gt_boxes, targets=None, response_mask=None):
+        ret = (self.dense_head(x, gt_boxes, targets=targets) if response_mask is None else
+               self.dense_head(x, gt_boxes, targets=targets, response_mask=response_mask))
         # precomputed targets are cleaned by whoever built them and say so (train.DistillStep.prep); anything else is cleaned here
         if self.training and "box_encoding" in ret and not (targets is not None and targets.get("box_encoding_clean")):
             for enc in ret["box_encoding"].values():
@@ -122,7 +123,7 @@ class BEVFusionCenterHead(nn.Module):
 
     def forward(self, lidar_points=None, cameras_imgs=None, metas=None, gt_boxes=None,
                 return_feature=False, targets=None, loss_norm=None, lidar_prepared=None, depth_label=None,
-                depth_weight=None, return_depth_logits=False, **_):
+                depth_weight=None, return_depth_logits=False, response_mask=None, **_):
         """targets / loss_norm: optional precomputed FCOS targets and globally reduced loss
         normalisers (train.py computes them up front so the network pass holds no collective);
         lidar_prepared: LidarEncoder.prepare(lidar_points), when the caller ran it ahead of time;
@@ -144,7 +145,8 @@ class BEVFusionCenterHead(nn.Module):
         bev, bev_out = feature_tap(bev) if tapped else (bev, bev)
         trunk, _ = self.bev_encoder(bev)
         trunk, trunk_out = feature_tap(trunk) if tapped else (trunk, trunk)
-        ret = self.det_head(trunk, gt_boxes, targets=targets)
+        # response_mask (train.DistillStep.teacher): the head maps are read weighted by it only -- feature requests alone
+        ret = self.det_head(trunk, gt_boxes, targets=targets, response_mask=response_mask if return_feature else None)
         if return_feature:
             return bev, trunk, ret["multi_head_features"]
         if self.training:

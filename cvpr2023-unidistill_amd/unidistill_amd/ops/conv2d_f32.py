@@ -368,6 +368,38 @@ def conv3x3_inference(x, weight, bias=None, scale=None, shift=None, relu=False):
         return _launch3(_nhwc(x), weight, b, relu=relu, scale=scale, shift=shift)
 
 
+def units_supported(x, weight):
+    """conv3x3_units takes this layer: the F(4x4) kernel is the one that walks a unit list."""
+    return supported(x, weight, 3) and wino4_pays(x.shape[2], x.shape[3], weight.shape[1], weight.shape[0])
+
+
+def unit_block_pixels(H, W):
+    """(width, height) in pixels of the F(4x4) launch plan's pixel units (32-tile blocks) on an H x W map."""
+    shape = _lib.load().ud_conv3x3_wino4_f32_block_shape(H, W)
+    return 4 * (shape >> 8), 4 * (shape & 255)
+
+
+def conv3x3_units(x, weight, bias, units, y=None):
+    """conv3x3_inference over the listed pixel units only (ud_conv3x3_wino4_units_nhwc_f32).  units: i32 device tensor, count then
+    ascending block indices (ops/head_sites.py).  Blocks that are not listed are not computed: there y keeps what it held (a fresh
+    y: uninitialised memory), so the consumer must read listed blocks only."""
+    with torch.no_grad():
+        _lib.require_gpu(x, weight, units)
+        x = _nhwc(x)
+        B, cin, H, W = x.shape
+        cout = weight.shape[0]
+        assert units_supported(x, weight) and units.dtype == torch.int32
+        lib = _lib.load()
+        if y is None:
+            y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        b = None if bias is None else bias.detach().float().contiguous()
+        U = _wino_weights(weight, False, f4=True)
+        ws = _lib.workspace(x.device, lib.ud_conv3x3_wino4_f32_workspace_bytes(B, H, W, cin, cout), "conv_w4")
+        _lib.ud.ud_conv3x3_wino4_units_nhwc_f32(x, U, y, B, H, W, cin, cout, b, None, None, None, 0, units.data_ptr() + 4,
+                                                units, ws, ws.numel(), _lib.stream_of(x))
+        return y
+
+
 def conv1x1(x, weight, bias=None, bn_stats=False):
     return _apply(x, weight, bias, 1, False, bn_stats)
 

@@ -134,6 +134,26 @@ class _BnReluGroupTail(torch.autograd.Function):
         return dy, dgamma, dbeta, None, None, None, None, None, None, None, dw, db, None, None
 
 
+def bn_relu_group_tail_sites(y, gamma, beta, running_mean, running_var, eps, weight, bias, G, KM, sites):
+    """Eval-mode, no-grad bn_relu_group_tail for a consumer that weights every site by sites.mask (ops/head_sites.py): the dense
+    result where mask > 0, exactly 0 elsewhere (ud_head_tail_f32_bn_fwd_sites).  Of y only the mask sites' 3 x 3 neighbourhoods are
+    read for values that count, so y may come from conv3x3_units with sites.conv_units."""
+    with torch.no_grad():
+        _lib.require_gpu(y, weight, sites.mask)
+        assert y.is_contiguous(memory_format=torch.channels_last) and y.dtype == torch.float32
+        B, C, H, W = y.shape
+        assert C == G * 64 and weight.shape == (G * KM, 64, 3, 3) and tuple(sites.mask.shape) == (B, H, W)
+        assert sites.strip == (16, _lib.load().ud_head_tail_f32_strip_rows(B, H, W, G, KM))
+        vec = bn_act.batch_stats(y, gamma, beta, running_mean, running_var, False, None, eps)
+        v0, row = vec.data_ptr(), 4 * C
+        wt = weight.detach().permute(0, 2, 3, 1).contiguous()          # [G*KM, 3, 3, 64] = [G][KM][9][64]
+        z = torch.empty((B, G * KM, H, W), dtype=torch.float32, device=y.device, memory_format=torch.channels_last)
+        b = None if bias is None else bias.detach().contiguous()
+        _lib.ud.ud_head_tail_f32_bn_fwd_sites(y, v0 + 3 * row, v0 + 4 * row, wt, b, z, B, H, W, G, KM, sites.mask, sites.tail_rows,
+                                              _lib.stream_of(y))
+        return z
+
+
 def bn_relu_group_tail(y, gamma, beta, running_mean, running_var, training, momentum, eps, tracked, partial, weight, bias, G, KM):
     return _BnReluGroupTail.apply(y, gamma, beta, running_mean, running_var, training, momentum, eps, tracked, partial,
                                   weight, bias, G, KM)

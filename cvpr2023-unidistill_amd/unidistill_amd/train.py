@@ -177,7 +177,8 @@ class DistillStep(nn.Module):
     def teacher(self, batch, prep, lidar_prepared=None):
         bufs = self._reset_teacher_buffers() if (self.teacher_train_mode and self.teacher_model.training) else None
         out = self.teacher_model(self._points(batch), batch.get("imgs"), batch.get("mats_dict"),
-                                 prep["gt"], return_feature=True, lidar_prepared=lidar_prepared)
+                                 prep["gt"], return_feature=True, lidar_prepared=lidar_prepared,
+                                 response_mask=prep["mask"])
         if bufs is not None:
             self._note_teacher_versions(bufs)      # what the teacher pass itself left: anything newer came from outside
         return out

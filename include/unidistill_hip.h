@@ -463,6 +463,23 @@ int ud_head_tail_f32_bn_fwd(const float* a, const float* bn_scale, const float* 
                             float* z, int B, int H, int W, int G, int KM, ud_stream_t stream);
 int ud_head_tail_f32_bn_wgrad(const float* a, const float* bn_scale, const float* bn_shift, const float* dz, float* dw, int B,
                               int H, int W, int G, int KM, void* workspace, size_t workspace_bytes, ud_stream_t stream);
+/* ud_head_tail_f32_bn_fwd for a consumer that weights every site by mask f32 [B][H][W] (the frozen distillation teacher): z is
+ * the dense result where mask > 0 and exactly 0 elsewhere.  strip_rows [strips][2] = the (first, end) image rows of each strip
+ * (16 columns x ud_head_tail_f32_strip_rows rows, index (b * strips_down + sy) * strips_across + sx) that hold a site, end <=
+ * first for none, from ud_head_sites_build: a workgroup walks those rows only and writes zeros to the rest of its strip without
+ * reading a.  Of a, only the sites with mask > 0 and their eight neighbours are needed. */
+int ud_head_tail_f32_strip_rows(int B, int H, int W, int G, int KM);
+int ud_head_tail_f32_bn_fwd_sites(const float* a, const float* bn_scale, const float* bn_shift, const float* w, const float* bias,
+                                  float* z, int B, int H, int W, int G, int KM, const float* mask, const int* strip_rows,
+                                  ud_stream_t stream);
+/* One launch: mask f32 [B][H][W] -> the work lists of the two launches above, on the device, in ascending index order.
+ *   conv_units  i32 [1 + blocks]   count, then the blk_w x blk_h pixel blocks whose rectangle, grown by one pixel (the tail is a
+ *                                  3x3 convolution), holds a site with mask > 0
+ *   tail_strips i32 [1 + strips]   count, then the strip_w x strip_h pixel strips that hold such a site
+ *   tail_rows   i32 [strips][2]    (first, end) image rows of those sites per strip, (0, 0) for none
+ *   scratch     i32 [1 + blocks + strips], zero on entry */
+int ud_head_sites_build(const float* mask, int B, int H, int W, int blk_w, int blk_h, int strip_w, int strip_h, int* conv_units,
+                        int* tail_strips, int* tail_rows, int* scratch, ud_stream_t stream);
 /* Backward of relu(bn(y)) -> second convolutions down to y in two passes that RECOMPUTE the tail's data gradient instead of
  * storing it: dgamma / dbeta [G*64] (training-mode statistics: mean / invstd of y, folded scale / shift) and dy [B, H, W, G*64].
  * dy_colsum (optional, [G*64]): the per-channel sums of the dy values stored, in a fixed order -- the bias gradient of the
@@ -634,6 +651,16 @@ int ud_conv3x3_wino4_nhwc_f32(const float* x, const float* U, float* y, int B, i
                               const float* bias, const float* scale, const float* shift, const float* residual, int flags,
                               float* partial, size_t partial_bytes, int* slices, void* workspace, size_t workspace_bytes,
                               ud_stream_t stream);
+/* The same launch restricted to a device-side list of its pixel units (32-tile blocks, index (b * by + iy) * bx + ix of the plan's
+ * bx x by blocks per image; ud_conv3x3_wino4_f32_block_shape = (tiles across << 8) | tiles down of a block): unit_list holds
+ * *unit_count block indices in ascending order.  The grid is the dense launch's; the persistent workgroups read the count and
+ * walk (listed block, output-channel block) units only -- whole units, stream-K tail and fix-up as in the dense schedule.  Blocks
+ * that are not listed are neither read nor written: their part of y keeps what it held.  Inference only (no BatchNorm sums). */
+int ud_conv3x3_wino4_f32_block_shape(int H, int W);
+int ud_conv3x3_wino4_units_nhwc_f32(const float* x, const float* U, float* y, int B, int H, int W, int Cin, int Cout,
+                                    const float* bias, const float* scale, const float* shift, const float* residual, int flags,
+                                    const int* unit_list, const int* unit_count, void* workspace, size_t workspace_bytes,
+                                    ud_stream_t stream);
 
 /* Weight gradient of the same layers through the Winograd form (gradient of ud_conv3x3_wino_nhwc_f32: 16 instead of 36 multiplications
  * per 2 x 2 tile and (n, c)); same contract as ud_conv3x3_wgrad_nhwc_f32: dw [Cout][3][3][Cin], tile slices reduced in a fixed order. */
