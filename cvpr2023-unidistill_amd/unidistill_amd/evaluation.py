@@ -43,6 +43,10 @@ DETECTION_CVPR_2019 = {
     "max_boxes_per_sample": 500,
     "mean_ap_weight": 5,
 }
+# The nuScenes tracking classes and CenterPoint's per-class association radius in metres (NuScenesTracker).
+TRACKING_NAMES = ["bicycle", "bus", "car", "motorcycle", "pedestrian", "trailer", "truck"]
+TRACKING_MAX_DIST = {"car": 4.0, "truck": 4.0, "bus": 5.5, "trailer": 3.0, "pedestrian": 1.0, "motorcycle": 13.0,
+                     "bicycle": 3.0}
 
 
 def attr_id(name):
@@ -393,6 +397,14 @@ class NuScenesDetectionEval:
         summary["cfg"] = dict(self.cfg)
         return summary
 
+    def last_predictions(self):
+        """What the last ``compute()`` evaluated, for consumers of the rows (``NuScenesTracker``): (pred, layout) on rank 0 --
+        pred["rec"] f64 [rows, 10] and pred["cls"] i32 [rows] on the device, layout["start"] / ["count"] per sample on the host
+        -- and None on the other ranks.  Raises if ``compute()`` has not run since the last reset."""
+        if not self._computed:
+            raise RuntimeError("no evaluated predictions: call compute() first")
+        return self._last
+
     def write_submission(self, path, sample_tokens):
         """The devkit's results JSON (generate_submission_results with meta_type_list ["use_camera", "use_lidar"]):
         sample_tokens[s] names sample s.  ``rotation`` is the yaw-only quaternion [cos(yaw/2), 0, 0, sin(yaw/2)]; the
@@ -418,6 +430,90 @@ class NuScenesDetectionEval:
                               "velocity": x[7:9].tolist(), "detection_name": self.class_names[cls[r]],
                               "detection_score": float(x[9]),
                               "attribute_name": ATTRIBUTE_NAMES[attr[r]] if attr[r] >= 0 else ""})
+            results[tok] = boxes
+        sub = {"meta": {"use_camera": True, "use_lidar": True, "use_radar": False, "use_map": False,
+                        "use_external": False}, "results": results}
+        with open(path, "w") as f:
+            json.dump(sub, f)
+        return sub
+
+
+class NuScenesTracker:
+    """CenterPoint's greedy, velocity-compensated centre tracker over the predictions a ``NuScenesDetectionEval`` holds on the
+    device (ops/tracking.py): a detector's validation run becomes a nuScenes tracking submission.
+
+        tr = NuScenesTracker()
+        ids = tr.track(evaluator, scene, timestamp_us)      # after evaluator.compute(); one launch for all scenes
+        tr.write_submission(path, sample_tokens)
+
+    ``max_dist``: {class name: metres}, None = ``TRACKING_MAX_DIST``; a class is tracked iff it has an entry.  Differences from
+    CenterPoint's pub_tracker.py, by design: a track coasts by the current frame's dt (not by the dt of the frame that last saw
+    it); detections are matched in descending score order (equal scores in row order) and equal distances go to the track
+    earlier in the list.  Coasting tracks are not emitted."""
+
+    def __init__(self, class_names=CLASS_NAMES, max_dist=None, max_age=3, score_threshold=0.0):
+        from .ops import tracking as T
+        self.class_names = list(class_names)
+        if max_dist is None:
+            max_dist = TRACKING_MAX_DIST
+        elif any(n not in self.class_names for n in max_dist):
+            raise ValueError(f"max_dist names classes that are not in class_names: "
+                             f"{[n for n in max_dist if n not in self.class_names]}")
+        self.track_class = [n in max_dist for n in self.class_names]
+        self.max_dist = [float(max_dist.get(n, 0.0)) for n in self.class_names]
+        self.max_age, self.score_threshold = int(max_age), float(score_threshold)
+        if not 1 <= len(self.class_names) <= T.MAX_CLASSES:
+            raise ValueError(f"1 .. {T.MAX_CLASSES} classes supported, got {len(self.class_names)}")
+        if not 1 <= self.max_age <= T.MAX_AGE:
+            raise ValueError(f"max_age must be in 1 .. {T.MAX_AGE}, got {max_age}")
+        self._result = None
+
+    def track(self, evaluator, scene, timestamp_us):
+        """scene [S] (an integer per sample) and timestamp_us [S] (int64) for the evaluator's S samples -> {"track_id",
+        "track_hits"}: int32 device tensors aligned with the evaluator's prediction rows (0 = not tracked).  Rank 0 under
+        torch.distributed; None on the other ranks, without any collective.  Raises if ``compute()`` has not run, and
+        ValueError on a non-zero device status (a non-finite velocity, for instance: 7-value boxes carry none)."""
+        from .ops import tracking as T
+        self._result = None
+        last = evaluator.last_predictions()
+        if last is None:
+            return None
+        pred, layout = last
+        S = evaluator.num_samples
+        scene = np.asarray(scene, dtype=np.int64).reshape(-1)
+        if len(scene) != S or len(np.asarray(timestamp_us).reshape(-1)) != S:
+            raise ValueError(f"scene and timestamp_us need one entry for each of the {S} samples")
+        frame_sample, scene_off, frame_dt = T.scene_frames(scene, timestamp_us)
+        ids, hits, status = T.track_scenes(pred["rec"], pred["cls"], layout["start"], layout["count"], frame_sample, scene_off,
+                                           frame_dt, track_class=self.track_class, max_dist=self.max_dist,
+                                           max_age=self.max_age, score_threshold=self.score_threshold)
+        status = int(status.item())
+        if status:
+            raise ValueError(f"nuScenes tracking: {T.status_text(status)}")
+        self._result = (pred, layout, ids, scene)
+        return {"track_id": ids, "track_hits": hits}
+
+    def write_submission(self, path, sample_tokens):
+        """The devkit's tracking results JSON of the last ``track()``: per tracked row sample_token, translation, size, rotation
+        (the detection file's yaw-only quaternion), velocity, tracking_id "{scene}_{id}", tracking_name, tracking_score (the
+        detection score); a sample without a tracked box maps to [].  The other ranks write nothing and get None."""
+        if self._result is None:
+            return None
+        pred, layout, ids, scene = self._result
+        if len(sample_tokens) != len(scene):
+            raise ValueError(f"{len(sample_tokens)} sample tokens for {len(scene)} samples")
+        rec, cls, ids = pred["rec"].cpu().numpy(), pred["cls"].cpu().numpy(), ids.cpu().numpy()
+        results = {}
+        for s, tok in enumerate(sample_tokens):
+            boxes = []
+            for r in range(layout["start"][s], layout["start"][s] + layout["count"][s]):
+                if ids[r] <= 0:
+                    continue
+                x = rec[r]
+                boxes.append({"sample_token": tok, "translation": x[0:3].tolist(), "size": x[3:6].tolist(),
+                              "rotation": [float(np.cos(x[6] / 2)), 0.0, 0.0, float(np.sin(x[6] / 2))],
+                              "velocity": x[7:9].tolist(), "tracking_id": f"{int(scene[s])}_{int(ids[r])}",
+                              "tracking_name": self.class_names[cls[r]], "tracking_score": float(x[9])})
             results[tok] = boxes
         sub = {"meta": {"use_camera": True, "use_lidar": True, "use_radar": False, "use_map": False,
                         "use_external": False}, "results": results}

@@ -1354,6 +1354,49 @@ int ud_box_fusion(const float* rois, const float* scores, const long long* label
                   int max_out, float* out_rois, float* out_scores, long long* out_labels, int* out_num, int* status,
                   int* out_anchor, int* out_members, void* workspace, size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- Multi-object tracking of the validation predictions (csrc/track.hip) -----------------------------------
+ * CenterPoint's greedy, velocity-compensated centre association over the rows of ud_nus_pred_to_global, every scene in one
+ * launch (one workgroup per scene, its frames in order); tests/tracking_reference.py restates it in numpy.  Nothing
+ * synchronises with the host, no allocation, no floating-point atomics, bitwise reproducible.
+ *   rec / cls            DEVICE f64[num_rows][UD_NUS_PRED_COLS] / i32[num_rows]: the evaluator's prediction rows.
+ *   row_start / row_count  DEVICE i64[num_samples]: sample s owns rows row_start[s] .. + row_count[s] (samples in any order).
+ *   frame_sample         DEVICE i64[num_frames]: the sample of every frame, scene after scene, each scene's frames in time order.
+ *   scene_off            DEVICE i64[num_scenes + 1]: scene k = frames scene_off[k] .. scene_off[k + 1].
+ *   frame_dt             DEVICE f64[num_frames]: seconds since the scene's previous frame, 0 for its first.
+ * Per scene: no tracks, id counter 0.  Per frame: (1) candidates = rows with track_class[cls] and score >= score_threshold, by
+ * descending score, equal scores by ascending row; such a row with a non-finite translation, velocity or score sets
+ * UD_TRACK_ST_NONFINITE and is no candidate.  (2) every track coasts: ct = ct + v * dt in x and y, a rounded multiply then a
+ * rounded add.  (3) candidates in order: among the unclaimed tracks of the candidate's class, d2 = dx * dx + dy * dy to the
+ * coasted centre; the smallest d2 wins, the lowest slot on a tie, and is claimed if d2 <= max_dist[cls] * max_dist[cls].
+ * (4) the new list: one entry per candidate in order (a match keeps the id, hits = hits + 1 if the track was seen in the
+ * previous frame and 1 otherwise; no match: the next id, from 1 per scene, hits = 1; centre, velocity and class of the
+ * detection, age 0), then the unclaimed tracks in their old order with age + 1, dropped when that reaches max_age.
+ * Outputs (DEVICE, i32[num_rows]): track_id (0: the row is no candidate of a listed frame) and track_hits; *status i32, OR-ed:
+ * UD_TRACK_ST_NONFINITE; UD_TRACK_ST_COUNT (a frame with more than UD_NUS_MAX_BOXES rows: treated as empty); UD_TRACK_ST_RANGE
+ * (a frame's sample, a sample's rows or a scene's frames outside the inputs: treated as empty).
+ * UD_ERR_INVALID_ARG with nothing launched: num_scenes < 1, max_age outside 1 .. UD_TRACK_MAX_AGE, num_classes outside 1 ..
+ * UD_NUS_MAX_CLASSES, num_rows >= 2^31, a NaN threshold, a NaN or negative max_dist of a tracked class, a missing pointer;
+ * UD_ERR_WORKSPACE: less than ud_track_workspace_bytes(num_scenes, max_age) (0 for sizes out of range). */
+#define UD_TRACK_MAX_AGE 8
+#define UD_TRACK_ST_NONFINITE 1
+#define UD_TRACK_ST_COUNT 2
+#define UD_TRACK_ST_RANGE 4
+
+typedef struct {
+  int num_classes;
+  int max_age;
+  int64_t num_rows, num_samples, num_frames, num_scenes;
+  double score_threshold;
+  double max_dist[UD_NUS_MAX_CLASSES];        /* metres, per class */
+  uint8_t track_class[UD_NUS_MAX_CLASSES + 1]; /* non-zero: the class is tracked */
+} UdTrackCfg;
+
+size_t ud_track_workspace_bytes(int64_t num_scenes, int max_age);
+int ud_track_scenes(const double* rec, const int32_t* cls, const int64_t* row_start, const int64_t* row_count,
+                    const int64_t* frame_sample, const int64_t* scene_off, const double* frame_dt,
+                    const UdTrackCfg* cfg_host, int32_t* track_id, int32_t* track_hits, int32_t* status, void* workspace,
+                    size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
