@@ -47,6 +47,20 @@ DETECTION_CVPR_2019 = {
 TRACKING_NAMES = ["bicycle", "bus", "car", "motorcycle", "pedestrian", "trailer", "truck"]
 TRACKING_MAX_DIST = {"car": 4.0, "truck": 4.0, "bus": 5.5, "trailer": 3.0, "pedestrian": 1.0, "motorcycle": 13.0,
                      "bicycle": 3.0}
+# The devkit's tracking_nips_2019 config as NuScenesTrackingEval reads it.
+TRACKING_NIPS_2019 = {
+    "tracking_names": TRACKING_NAMES,
+    "class_range": {"car": 50, "truck": 50, "bus": 50, "trailer": 50, "pedestrian": 40, "motorcycle": 40, "bicycle": 40},
+    "dist_fcn": "center_distance",
+    "dist_th_tp": 2.0,
+    "min_recall": 0.1,
+    "num_thresholds": 40,
+    "max_boxes_per_sample": 500,
+    "frame_period_s": 0.5,
+    "metric_worst": {"amota": 0.0, "amotp": 2.0, "recall": 0.0, "motar": 0.0, "gt": -1, "mota": 0.0, "motp": 2.0, "mt": 0.0,
+                     "ml": -1, "faf": 500, "tp": 0.0, "fp": -1, "fn": -1, "ids": -1, "frag": -1, "tid": 20, "lgd": 20},
+}
+TRACKING_SUMMED = ("mt", "ml", "tp", "fp", "fn", "ids", "frag", "gt")
 
 
 def attr_id(name):
@@ -467,6 +481,7 @@ class NuScenesTracker:
         if not 1 <= self.max_age <= T.MAX_AGE:
             raise ValueError(f"max_age must be in 1 .. {T.MAX_AGE}, got {max_age}")
         self._result = None
+        self._tracked = False       # track() has run (its result is None off rank 0)
 
     def track(self, evaluator, scene, timestamp_us):
         """scene [S] (an integer per sample) and timestamp_us [S] (int64) for the evaluator's S samples -> {"track_id",
@@ -474,9 +489,10 @@ class NuScenesTracker:
         torch.distributed; None on the other ranks, without any collective.  Raises if ``compute()`` has not run, and
         ValueError on a non-zero device status (a non-finite velocity, for instance: 7-value boxes carry none)."""
         from .ops import tracking as T
-        self._result = None
+        self._result, self._tracked = None, False
         last = evaluator.last_predictions()
         if last is None:
+            self._tracked = True
             return None
         pred, layout = last
         S = evaluator.num_samples
@@ -490,8 +506,16 @@ class NuScenesTracker:
         status = int(status.item())
         if status:
             raise ValueError(f"nuScenes tracking: {T.status_text(status)}")
-        self._result = (pred, layout, ids, scene)
+        self._result, self._tracked = (pred, layout, ids, scene), True
         return {"track_id": ids, "track_hits": hits}
+
+    def last_tracks(self):
+        """What the last ``track()`` stored, for consumers of the ids (``NuScenesTrackingEval``): (pred, layout, ids, scene) on
+        rank 0 -- the evaluator's rows and layout, the int32 ids on the device, the scene per sample -- and None on the other
+        ranks.  Raises before ``track()``."""
+        if not self._tracked:
+            raise RuntimeError("no tracks: call track() first")
+        return self._result
 
     def write_submission(self, path, sample_tokens):
         """The devkit's tracking results JSON of the last ``track()``: per tracked row sample_token, translation, size, rotation
@@ -520,6 +544,171 @@ class NuScenesTracker:
         with open(path, "w") as f:
             json.dump(sub, f)
         return sub
+
+
+def tracking_pass_metrics(counts, dist_sum, valid, recall, frame_period_s):
+    """One class: counts int64 [K + 1, 12] (ops.track_metric.COUNTS), dist_sum / valid [K + 1] (entry 0 = all boxes), recall [K]
+    -> {metric: float64 [K]} over the threshold passes, NaN where the pass was not run."""
+    c = {n: counts[1:, i].astype(np.float64) for i, n in enumerate(("frames", "objects", "matches", "switches", "fp", "miss",
+                                                                   "mt", "ml", "frag", "tid", "lgd", "inst"))}
+    ok = np.asarray(valid[1:]) != 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        P, tp = c["objects"], c["matches"] + c["switches"]
+        fp, fn, ids = c["fp"], c["miss"], c["switches"]
+        m = {"tp": tp, "fp": fp, "fn": fn, "ids": ids, "gt": P, "recall": tp / P,
+             "mota": np.maximum(0.0, 1.0 - (fn + ids + fp) / P),
+             "motar": np.where(tp > 0, np.maximum(0.0, 1.0 - (ids + fp + fn - (1.0 - tp / P) * P) / (tp / P * P)), np.nan),
+             "motp": np.where(tp > 0, np.asarray(dist_sum[1:], np.float64) / tp, np.nan), "faf": 100.0 * fp / c["frames"],
+             "mt": c["mt"], "ml": c["ml"], "frag": c["frag"],
+             "tid": np.where(c["inst"] > 0, c["tid"] / c["inst"] * frame_period_s, np.nan),
+             "lgd": np.where(c["inst"] > 0, c["lgd"] / c["inst"] * frame_period_s, np.nan)}
+    return {k: np.where(ok, v, np.nan) for k, v in m.items()}
+
+
+def summarize_tracking(curves, names, cfg):
+    """``NuScenesTrackingEval.last_curves()`` -> the devkit's tracking summary: per class amota / amotp over the thresholds (NaN
+    -> the worst value) and every other metric at the threshold of the best mota; over the classes sums of the counts and means
+    of the rest, NaN-aware."""
+    worst = cfg["metric_worst"]
+    label = {m: {} for m in worst}
+    for t, name in enumerate(names):
+        pm = tracking_pass_metrics(curves["counts"][t], curves["dist_sum"][t], curves["valid"][t], curves["recall"],
+                                   cfg["frame_period_s"])
+        if np.all(np.isnan(pm["mota"])):
+            for m, w in worst.items():
+                label[m][name] = float("nan") if w == -1 else float(w)
+            continue
+        best = int(np.nanargmax(pm["mota"]))
+        label["amota"][name] = float(np.mean(np.where(np.isnan(pm["motar"]), worst["amota"], pm["motar"])))
+        label["amotp"][name] = float(np.mean(np.where(np.isnan(pm["motp"]), worst["amotp"], pm["motp"])))
+        for m, v in pm.items():
+            label[m][name] = float(v[best])
+    summary = {"label_metrics": label}
+    for m in worst:
+        vals = np.array(list(label[m].values()), dtype=np.float64)
+        if np.all(np.isnan(vals)):
+            summary[m] = float("nan")
+        else:
+            summary[m] = float(np.nansum(vals)) if m in TRACKING_SUMMED else float(np.nanmean(vals))
+    return summary
+
+
+class NuScenesTrackingEval:
+    """The nuScenes tracking metric (AMOTA, AMOTP, MOTA, IDS ...) over the tracks a ``NuScenesTracker`` holds on the device,
+    without the devkit (ops/track_metric.py).
+
+        ev = NuScenesTrackingEval(class_names=CLASS_NAMES, cfg=TRACKING_NIPS_2019, device=dev)
+        ev.add_ground_truth(translation, cls, instance, num_pts, sample, ego_translation, scene, timestamp_us)
+        summary = ev.compute(tracker)     # after tracker.track(evaluator, ...); rank 0, None on the other ranks, no collective
+
+    Classes of ``class_names`` outside cfg["tracking_names"] are ignored.  The tracks are scored as given: the devkit's linear
+    interpolation across missed frames and its bike-rack filter (``keep`` stands in for it) are not ported."""
+
+    def __init__(self, class_names=CLASS_NAMES, cfg=TRACKING_NIPS_2019, device=None):
+        from .ops import track_metric as M
+        self.class_names = list(class_names)
+        self.cfg = dict(cfg)
+        if not 1 <= len(self.class_names) <= M.MAX_CLASSES:
+            raise ValueError(f"1 .. {M.MAX_CLASSES} classes supported, got {len(self.class_names)}")
+        self.track_class = [n in self.cfg["tracking_names"] for n in self.class_names]
+        if not any(self.track_class):
+            raise ValueError("none of class_names is in cfg['tracking_names']")
+        missing = [n for n, t in zip(self.class_names, self.track_class) if t and n not in self.cfg["class_range"]]
+        if missing:
+            raise ValueError(f"cfg['class_range'] has no range for {missing}")
+        if not 1 <= self.cfg["num_thresholds"] <= M.MAX_THRESHOLDS:
+            raise ValueError(f"num_thresholds must be in 1 .. {M.MAX_THRESHOLDS}")
+        self.class_range = [float(self.cfg["class_range"].get(n, 0.0)) for n in self.class_names]
+        self.recall = np.round(np.linspace(self.cfg["min_recall"], 1.0, self.cfg["num_thresholds"]), 12)
+        self.device = _lib_device(device)
+        self.gt = None
+        self._curves = None
+
+    def add_ground_truth(self, translation, cls, instance, num_pts, sample, ego_translation, scene, timestamp_us, keep=None):
+        """Global-frame GT: translation [G, 3], class id [G], instance [G] (int64, unique per object over the split), num_pts
+        [G], sample index [G] in 0 .. S-1; per sample ego_translation [S, 3], scene [S], timestamp_us [S]; keep [G] (bool,
+        optional): the caller's filter.  Replaces any earlier ground truth."""
+        ego = np.asarray(ego_translation, dtype=np.float64).reshape(-1, 3)
+        S = len(ego)
+        sample = np.asarray(sample, dtype=np.int64).reshape(-1)
+        G = len(sample)
+        cls = np.asarray(cls, dtype=np.int64).reshape(-1)
+        instance = np.asarray(instance, dtype=np.int64).reshape(-1)
+        num_pts = np.asarray(num_pts, dtype=np.int64).reshape(-1)
+        keep = np.ones(G, dtype=bool) if keep is None else np.asarray(keep, dtype=bool).reshape(-1)
+        xyz = np.asarray(translation, dtype=np.float64).reshape(G, 3)
+        scene = np.asarray(scene, dtype=np.int64).reshape(-1)
+        ts = np.asarray(timestamp_us, dtype=np.int64).reshape(-1)
+        if S < 1 or len(scene) != S or len(ts) != S:
+            raise ValueError("ground truth needs ego_translation [S, 3], scene [S] and timestamp_us [S] for S >= 1 samples")
+        if not (len(cls) == len(instance) == len(num_pts) == len(keep) == G):
+            raise ValueError("ground-truth columns differ in length")
+        if G and (sample.min() < 0 or sample.max() >= S):
+            raise ValueError(f"ground-truth sample index outside 0 .. {S - 1}")
+        if G and (cls.min() < 0 or cls.max() >= len(self.class_names)):
+            raise ValueError(f"ground-truth class id outside 0 .. {len(self.class_names) - 1}")
+        order = np.argsort(sample, kind="stable")
+        off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum(np.bincount(sample, minlength=S), out=off[1:])
+        d = self.device
+        self.gt = {"xyz": torch.from_numpy(np.ascontiguousarray(xyz[order])).to(d),
+                   "cls": torch.from_numpy(cls[order].astype(np.int32)).to(d),
+                   "num_pts": torch.from_numpy(np.clip(num_pts[order], -1, 1 << 30).astype(np.int32)).to(d),
+                   "keep": torch.from_numpy(keep[order].astype(np.uint8)).to(d), "ego": torch.from_numpy(ego).to(d),
+                   "instance": instance[order], "off": off, "scene": scene, "timestamp_us": ts}
+        self.gt_order = order        # row r of the device GT = row gt_order[r] of the caller's arrays
+        self.num_samples = S
+
+    def compute_curves(self, tracker, events_pass=None):
+        """Runs the device metric over ``tracker.last_tracks()`` -> the device outputs of ops.track_metric.evaluate_tracks on rank
+        0, None on the other ranks."""
+        from .ops import track_metric as M
+        if self.gt is None:
+            raise RuntimeError("add_ground_truth() first")
+        last = tracker.last_tracks()
+        if last is None:
+            return None
+        pred, layout, ids, scene = last
+        g = self.gt
+        if len(scene) != self.num_samples or not np.array_equal(np.asarray(scene, np.int64), g["scene"]):
+            raise ValueError("the tracker's scene per sample differs from the ground truth's")
+        return M.evaluate_tracks(pred["rec"], pred["cls"], ids, layout["start"], layout["count"], g["xyz"], g["cls"],
+                                 g["num_pts"], g["keep"], g["instance"], g["off"], g["ego"], g["scene"], g["timestamp_us"],
+                                 track_class=self.track_class, class_range=self.class_range, recall=self.recall,
+                                 dist_th_tp=self.cfg["dist_th_tp"], max_boxes_per_sample=self.cfg["max_boxes_per_sample"],
+                                 events_pass=events_pass)
+
+    def compute(self, tracker):
+        """The tracking summary: summary["label_metrics"][metric][class] and summary[metric], plus eval_time and cfg (rank 0;
+        None on the other ranks, without any collective)."""
+        from .ops import track_metric as M
+        t0 = time.time()
+        self._curves = None
+        out = self.compute_curves(tracker)
+        if out is None:
+            return None
+        status = int(out["status"].item())
+        if status:
+            raise ValueError(f"nuScenes tracking eval: {M.status_text(status)}")
+        self._curves = {k: out[k].cpu().numpy() for k in ("counts", "dist_sum", "valid", "thresholds", "num_scores")}
+        self._curves["recall"] = self.recall.copy()
+        self._curves["classes"] = [self.class_names[c] for c in out["classes"]]
+        summary = summarize_tracking(self._curves, self._curves["classes"], self.cfg)
+        summary["eval_time"] = time.time() - t0
+        summary["cfg"] = dict(self.cfg)
+        return summary
+
+    def last_curves(self):
+        """The per (class, threshold) arrays of the last ``compute()`` on the host: counts [T, K + 1, 12], dist_sum, valid,
+        thresholds [T, K], num_scores [T], recall [K], classes (names); None off rank 0."""
+        return self._curves
+
+
+def _lib_device(device):
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise RuntimeError(f"unidistill_amd ops run on the GPU only (no CPU fallback); got device {device}")
+    return device
 
 
 def depth_figures(terms):

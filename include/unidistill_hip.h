@@ -1397,6 +1397,85 @@ int ud_track_scenes(const double* rec, const int32_t* cls, const int64_t* row_st
                     const UdTrackCfg* cfg_host, int32_t* track_id, int32_t* track_hits, int32_t* status, void* workspace,
                     size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- The nuScenes tracking metric (csrc/track_metric.hip) -----------------------------------------------------
+ * AMOTA, AMOTP, MOTA, IDS and the other figures of the devkit's TrackingEval over the rows and ids of ud_track_scenes, scored as
+ * given (no interpolation of tracks); tests/track_metric_reference.py restates it in float64 Python with scipy's assignment.
+ * Everything is enqueued on `stream` without a host wait; no allocation, no floating-point atomics, bitwise reproducible.
+ *   pred_rec / pred_cls / track_id   DEVICE f64[num_rows][UD_NUS_PRED_COLS] / i32 / i32: the evaluator's rows and their ids.
+ *   row_start / row_count            DEVICE i64[num_samples]: the prediction rows of sample s.
+ *   gt_xyz / gt_cls / gt_num_pts / gt_keep / gt_inst   DEVICE f64[num_gt][3] / i32 / i32 / u8 / i32, sorted by sample:
+ *                                    gt_inst numbers the object densely within its (scene, class), below max_instances; an
+ *                                    object appears at most once per sample.  gt_off DEVICE i64[num_samples + 1].
+ *   ego                              DEVICE f64[num_samples][3]; frame_sample / scene_off as for ud_track_scenes.
+ *   recall                           DEVICE f64[num_thresholds]: the recall thresholds r_k.
+ * ROWS.  A GT row is kept iff gt_keep, gt_num_pts > 0, its class is tracked and sqrt(dx * dx + dy * dy) to its sample's ego
+ * translation is <= class_range.  A prediction row is kept iff track_id > 0, its class is tracked and it passes the same test.
+ * A non-finite translation (or score) sets UD_TM_ST_NONFINITE and drops the row; a sample with more than max_boxes_per_sample
+ * kept predictions sets UD_TM_ST_BOXES; a kept row whose id exceeds max_scene_rows sets UD_TM_ST_ID and is dropped.
+ * TRACK SCORE.  A kept prediction row's score is the mean detection score over the kept rows of its (scene, id), summed in
+ * (frame, row) order, then divided.
+ * ONE PASS = (class c, scene, threshold theta or "all boxes"); its state m: GT instance -> track id last matched, empty at the
+ * scene's first frame, kept through frames that miss the object.  Per frame, in (timestamp, sample) order:
+ *   1 hypotheses = kept prediction rows of class c with score >= theta, objects = kept GT rows of class c; a frame with neither
+ *     is skipped and not counted.  d(o, h) = sqrt(dx * dx + dy * dy); a pair is admissible iff d < dist_th_tp (tested on d).
+ *   2 objects in GT row order: if m[o] exists and an unclaimed hypothesis with that id is admissible (the first such in row
+ *     order), the pair is a MATCH and both leave.
+ *   3 among the rest: the matching over admissible pairs with the most pairs, and among those the least sum of d.  A pair is a
+ *     SWITCH if m[o] exists and differs from the hypothesis' id, else a MATCH; m[o] = id.  Solver: objects and hypotheses
+ *     without an admissible partner leave; the smaller side becomes the rows of a shortest-augmenting-path assignment (rows in
+ *     order, forbidden pairs cost UD_TM_MAX_FRAME_ROWS * dist_th_tp + 1); equal reduced costs go to the lowest column.  Where
+ *     several matchings are optimal this fixes one, the same in every run.
+ *   4 unmatched objects are MISS, unmatched hypotheses FP.
+ * Per pass and scene: the UD_TM_COUNTS integers frames, objects, matches, switches, fp, miss, mt (tracked / appearances >= 0.8
+ * per instance), ml (< 0.2), frag (MISS after a tracked appearance, later tracked again: once per gap), tid (frames of the
+ * scene's list from the first to the first tracked appearance) and lgd (longest run of MISS appearances), both summed over the
+ * instances tracked at least once, and that instance count; dist_sum = the sum of d over MATCH and SWITCH pairs in (frame, GT
+ * row) order.  Scenes are then added in scene order (integers and dist_sum alike).
+ * THRESHOLDS.  s = the scores of the all-boxes pass's MATCH hypotheses, descending, n of them; P = objects; rec[i] = (i + 1) / P;
+ * theta_k = s[0] where r_k <= rec[0], s[j] at a knot, else s[j] + ((s[j+1] - s[j]) / (rec[j+1] - rec[j])) * (r_k - rec[j]) with
+ * rec[j] < r_k < rec[j+1]; NaN where r_k > n / P, P = 0 or n = 0: that pass is not run (valid = 0, zeros).
+ * Outputs (DEVICE): counts i64[T][num_thresholds + 1][UD_TM_COUNTS], dist_sum f64 and valid i32 [T][num_thresholds + 1] (T =
+ * tracked classes in class order; entry 0 = all boxes), thresholds f64[T][num_thresholds], num_scores i64[T] (n); with
+ * events_pass >= -1 (-1 = all boxes, k = threshold k, -2 = off) events_type i32[num_gt] (-1 not kept, 0 MISS, 1 MATCH, 2
+ * SWITCH) and events_row (the matched prediction row or -1) of that pass; *status i32, OR-ed (also UD_TM_ST_RANGE: a layout
+ * entry outside the inputs, treated as empty; UD_TM_ST_INTERNAL: the solver's guard).
+ * UD_ERR_INVALID_ARG with nothing launched: classes outside 1 .. UD_NUS_MAX_CLASSES or none tracked, num_thresholds outside
+ * 1 .. UD_TM_MAX_THRESHOLDS, max_frame_rows (the most GT or prediction rows of one sample) above UD_TM_MAX_FRAME_ROWS,
+ * max_instances above UD_TM_MAX_INSTANCES, a missing pointer, a bad dist_th_tp or range; UD_ERR_WORKSPACE as usual. */
+#define UD_TM_MAX_FRAME_ROWS 512
+#define UD_TM_MAX_INSTANCES 4096
+#define UD_TM_MAX_THRESHOLDS 64
+#define UD_TM_COUNTS 12
+#define UD_TM_ST_NONFINITE 1
+#define UD_TM_ST_BOXES 2
+#define UD_TM_ST_RANGE 4
+#define UD_TM_ST_ID 8
+#define UD_TM_ST_INTERNAL 16
+
+typedef struct {
+  int num_classes;
+  int num_thresholds;
+  int max_boxes_per_sample;
+  int events_pass;       /* -2 off, -1 the all-boxes pass, k the pass of threshold k */
+  int max_frame_rows;    /* the most GT rows, or prediction rows, of one sample */
+  int max_instances;     /* the most GT instances of one (scene, class) */
+  int64_t num_rows, num_gt, num_samples, num_frames, num_scenes;
+  int64_t max_scene_rows; /* the most prediction rows of one scene: ids lie in 1 .. max_scene_rows */
+  double dist_th_tp;
+  double class_range[UD_NUS_MAX_CLASSES];
+  int64_t class_gt[UD_NUS_MAX_CLASSES];        /* GT rows per class */
+  uint8_t track_class[UD_NUS_MAX_CLASSES + 1]; /* non-zero: the class is tracked */
+} UdTrackMetricCfg;
+
+size_t ud_track_metric_workspace_bytes(const UdTrackMetricCfg* cfg);
+int ud_track_metric(const double* pred_rec, const int32_t* pred_cls, const int32_t* track_id, const int64_t* row_start,
+                    const int64_t* row_count, const double* gt_xyz, const int32_t* gt_cls, const int32_t* gt_num_pts,
+                    const uint8_t* gt_keep, const int32_t* gt_inst, const int64_t* gt_off, const double* ego,
+                    const int64_t* frame_sample, const int64_t* scene_off, const double* recall,
+                    const UdTrackMetricCfg* cfg_host, int64_t* counts, double* dist_sum, int32_t* valid, double* thresholds,
+                    int64_t* num_scores, int32_t* events_type, int32_t* events_row, int32_t* status, void* workspace,
+                    size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
