@@ -601,11 +601,23 @@ class NuScenesTrackingEval:
         ev.add_ground_truth(translation, cls, instance, num_pts, sample, ego_translation, scene, timestamp_us)
         summary = ev.compute(tracker)     # after tracker.track(evaluator, ...); rank 0, None on the other ranks, no collective
 
-    Classes of ``class_names`` outside cfg["tracking_names"] are ignored.  The tracks are scored as given: the devkit's linear
-    interpolation across missed frames and its bike-rack filter (``keep`` stands in for it) are not ported."""
+    Classes of ``class_names`` outside cfg["tracking_names"] are ignored.  With ``interpolate=False`` (the default) the tracks
+    are scored as given.  ``interpolate=True`` first fills the holes of every predicted and every ground-truth track by linear
+    interpolation, as the devkit does between its filters and its metric (ops.track_metric.interpolate_tracks):
+    a re-acquired track then no longer costs a MISS and a FRAG per coasted frame, and a ground-truth object that drops to
+    ``num_pts == 0`` for a frame stays in the evaluation.  That costs one host wait (the output's size depends on the data).
+    ``interpolate_mode``: "devkit" -- the weight from the right timestamp, as the devkit is recalled to compute it (unverified)
+    -- or "linear"; they differ only where frames are unevenly spaced or a hole is longer than one frame.  The tracker's rows
+    and its submission file are never interpolated (the devkit interpolates when it loads the file).  The devkit's bike-rack
+    filter is not ported (``keep`` stands in for it)."""
 
-    def __init__(self, class_names=CLASS_NAMES, cfg=TRACKING_NIPS_2019, device=None):
+    def __init__(self, class_names=CLASS_NAMES, cfg=TRACKING_NIPS_2019, device=None, interpolate=False,
+                 interpolate_mode="devkit"):
         from .ops import track_metric as M
+        self.interpolate = bool(interpolate)
+        self.interpolate_mode = str(interpolate_mode)
+        if self.interpolate_mode not in M.MODES:
+            raise ValueError(f"interpolate_mode must be one of {sorted(M.MODES)}, got {interpolate_mode!r}")
         self.class_names = list(class_names)
         self.cfg = dict(cfg)
         if not 1 <= len(self.class_names) <= M.MAX_CLASSES:
@@ -660,7 +672,8 @@ class NuScenesTrackingEval:
         self.num_samples = S
 
     def compute_curves(self, tracker, events_pass=None):
-        """Runs the device metric over ``tracker.last_tracks()`` -> the device outputs of ops.track_metric.evaluate_tracks on rank
+        """Runs the device metric over ``tracker.last_tracks()`` -> the device outputs of ops.track_metric.evaluate_tracks (with
+        ``interpolate``: of evaluate_tracks_interpolated, whose events and src_row maps refer to the interpolated rows) on rank
         0, None on the other ranks."""
         from .ops import track_metric as M
         if self.gt is None:
@@ -672,35 +685,47 @@ class NuScenesTrackingEval:
         g = self.gt
         if len(scene) != self.num_samples or not np.array_equal(np.asarray(scene, np.int64), g["scene"]):
             raise ValueError("the tracker's scene per sample differs from the ground truth's")
-        return M.evaluate_tracks(pred["rec"], pred["cls"], ids, layout["start"], layout["count"], g["xyz"], g["cls"],
-                                 g["num_pts"], g["keep"], g["instance"], g["off"], g["ego"], g["scene"], g["timestamp_us"],
-                                 track_class=self.track_class, class_range=self.class_range, recall=self.recall,
-                                 dist_th_tp=self.cfg["dist_th_tp"], max_boxes_per_sample=self.cfg["max_boxes_per_sample"],
-                                 events_pass=events_pass)
+        extra = {"mode": self.interpolate_mode} if self.interpolate else {}
+        run = M.evaluate_tracks_interpolated if self.interpolate else M.evaluate_tracks
+        return run(pred["rec"], pred["cls"], ids, layout["start"], layout["count"], g["xyz"], g["cls"], g["num_pts"], g["keep"],
+                   g["instance"], g["off"], g["ego"], g["scene"], g["timestamp_us"], track_class=self.track_class,
+                   class_range=self.class_range, recall=self.recall, dist_th_tp=self.cfg["dist_th_tp"],
+                   max_boxes_per_sample=self.cfg["max_boxes_per_sample"], events_pass=events_pass, **extra)
 
     def compute(self, tracker):
-        """The tracking summary: summary["label_metrics"][metric][class] and summary[metric], plus eval_time and cfg (rank 0;
-        None on the other ranks, without any collective)."""
+        """The tracking summary: summary["label_metrics"][metric][class] and summary[metric], plus eval_time and cfg -- with
+        ``interpolate`` also "interpolate": True and "interpolate_mode" -- (rank 0; None on the other ranks, without any
+        collective)."""
         from .ops import track_metric as M
         t0 = time.time()
         self._curves = None
         out = self.compute_curves(tracker)
         if out is None:
             return None
-        status = int(out["status"].item())
+        if self.interpolate:                      # both status words in the one read
+            status, filled = (int(v) for v in torch.cat([out["status"], out["interp_status"]]).cpu())
+            if filled:
+                raise ValueError(f"nuScenes tracking eval: {M.interp_status_text(filled)}")
+        else:
+            status = int(out["status"].item())
         if status:
             raise ValueError(f"nuScenes tracking eval: {M.status_text(status)}")
         self._curves = {k: out[k].cpu().numpy() for k in ("counts", "dist_sum", "valid", "thresholds", "num_scores")}
         self._curves["recall"] = self.recall.copy()
         self._curves["classes"] = [self.class_names[c] for c in out["classes"]]
         summary = summarize_tracking(self._curves, self._curves["classes"], self.cfg)
+        if self.interpolate:
+            self._curves["num_interpolated_pred"] = out["num_interpolated_pred"]
+            self._curves["num_interpolated_gt"] = out["num_interpolated_gt"]
+            summary["interpolate"], summary["interpolate_mode"] = True, self.interpolate_mode
         summary["eval_time"] = time.time() - t0
         summary["cfg"] = dict(self.cfg)
         return summary
 
     def last_curves(self):
         """The per (class, threshold) arrays of the last ``compute()`` on the host: counts [T, K + 1, 12], dist_sum, valid,
-        thresholds [T, K], num_scores [T], recall [K], classes (names); None off rank 0."""
+        thresholds [T, K], num_scores [T], recall [K], classes (names), with ``interpolate`` also num_interpolated_pred /
+        num_interpolated_gt (the interpolated rows of the two sides); None off rank 0."""
         return self._curves
 
 

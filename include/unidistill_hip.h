@@ -1476,6 +1476,89 @@ int ud_track_metric(const double* pred_rec, const int32_t* pred_cls, const int32
                     int64_t* num_scores, int32_t* events_type, int32_t* events_row, int32_t* status, void* workspace,
                     size_t workspace_bytes, ud_stream_t stream);
 
+/* ---- Interpolation of tracks across missed frames (csrc/track_interp.hip) -------------------------------------
+ * What the devkit's tracking evaluation does to every ground-truth track and every predicted track after its filters and before
+ * it scores them; tests/track_interp_reference.py restates it in float64 Python.  Two calls, because the size of the output
+ * depends on the data: ud_track_interp_count (counts), then -- after the caller has read the counts and laid the output out --
+ * ud_track_interp_fill (rows).  Integer counting only, no floating-point atomics, every interpolated value is written by one
+ * thread from its two endpoints, bitwise reproducible, independent of what the workspace held before.
+ * A SIDE is the predictions or the ground truth.  Each side has rows in the evaluator's layout (float64 columns, cls, per sample
+ * a first row and a row count), an int32 track key per row (predictions: the tracker's track_id; GT: a number dense within the
+ * scene, below UD_TI_MAX_GT_KEYS, that the host derives from the instance), the frames of ud_track_scenes (frame_sample /
+ * scene_off) and frame_ts DEVICE i64[num_frames]: the timestamp in microseconds of every frame, strictly ascending in a scene.
+ *   1 KEPT ROWS.  A row is kept by exactly the rule of ud_track_metric, section ROWS (csrc/track_kept.h holds it, once):
+ *     predictions track_id > 0, class tracked, xy distance to the sample's ego translation <= class_range; GT gt_keep,
+ *     gt_num_pts > 0, class tracked, the same range test.  Such a row with a non-finite column (predictions: all
+ *     UD_NUS_PRED_COLS, GT: the translation) sets UD_TI_ST_NONFINITE and is dropped.  A kept row whose key lies outside
+ *     1 .. max_scene_rows (predictions) or 0 .. max_gt_keys - 1 (GT) sets UD_TI_ST_KEY and is dropped.  A sample with more
+ *     than max_boxes_per_sample kept predictions (the devkit's cap, tested here before interpolation) sets UD_TI_ST_BOXES.
+ *   2 TRACKS.  A track is the set of kept rows of one (scene, key).  A key may occur at most once per frame; a second
+ *     occurrence sets UD_TI_ST_DUPLICATE (the caller raises).
+ *   3 HOLES.  For every frame f of the scene strictly between a track's first and last kept appearance in which the track has no
+ *     kept row -- frames without any rows and frames whose own row of the track was dropped in step 1 included -- one
+ *     interpolated row is made from the nearest kept appearance before (L) and after (R).  Nothing is extrapolated before the
+ *     first or after the last appearance.  Holes have no length bound.
+ *   4 WEIGHT.  mode UD_TI_MODE_DEVKIT: w = double(t_R - t_f) / double(t_R - t_L); UD_TI_MODE_LINEAR: w = double(t_f - t_L) /
+ *     double(t_R - t_L); the timestamps are subtracted as int64 before the conversion.  The result is (1 - w) * L + w * R.  The
+ *     devkit mode restates the devkit's interpolate_tracks as recalled (the ratio from the right timestamp, applied to the right
+ *     box, which mirrors time inside a hole); that recollection is unverified, hence the second mode.  The two agree where the
+ *     hole is one frame in the middle of its neighbours.
+ *   5 COLUMNS.  Translation (3), size (3), velocity (2) and score are each (1 - w) * a + w * b in float64: 1 - w rounded, two
+ *     rounded products, one rounded sum, never a fused multiply-add.  Yaw is yaw_L + w * remainder(yaw_R - yaw_L, 2 pi) with
+ *     the IEEE remainder (the slerp of two z-axis quaternions along the shorter arc), not re-wrapped.  GT rows carry only the
+ *     translation.  An interpolated row takes the class of R and the key of the track; predictions take the interpolated score.
+ *   6 OUTPUT.  Each side's output holds only the kept original rows, in their original order, and after them each sample's
+ *     interpolated rows in ascending key.  (The order is part of the definition: the metric's dist_sum and the track mean score
+ *     are float sums in (frame, row) order.)
+ * ud_track_interp_count writes counts DEVICE i64[2 * num_samples + 2 + UD_NUS_MAX_CLASSES]: the output rows of every sample
+ * (predictions, then GT), the interpolated rows of the two sides, the GT output rows per class; and ORs into *status.
+ * ud_track_interp_fill takes, per side, out_start / out_count DEVICE i64[num_samples] (the caller's layout of exactly those
+ * counts; num_out_pred / num_out_gt rows in all) and writes out_rec f64[num_out_pred][UD_NUS_PRED_COLS] / out_xyz
+ * f64[num_out_gt][3], out_cls, out_key and out_src i32 (the original row, -1 for an interpolated row).  Inputs that give other
+ * counts than the layout holds set UD_TI_ST_RANGE; nothing is written outside a sample's out_count rows.
+ * UD_ERR_INVALID_ARG with nothing launched: classes outside 1 .. UD_NUS_MAX_CLASSES or none tracked, num_scenes < 1, more than
+ * UD_TM_MAX_FRAME_ROWS rows in a sample, max_gt_keys above UD_TI_MAX_GT_KEYS, a mode other than the two, a bad range or
+ * max_boxes_per_sample, a missing pointer; UD_ERR_WORKSPACE: less than ud_track_interp_workspace_bytes (0 for sizes out of
+ * range; it depends on num_out_pred / num_out_gt, which are 0 for the count call). */
+#define UD_TI_MAX_GT_KEYS 4096 /* = UD_TM_MAX_INSTANCES: the GT keys of the output serve ud_track_metric as gt_inst */
+#define UD_TI_MODE_DEVKIT 0
+#define UD_TI_MODE_LINEAR 1
+#define UD_TI_ST_NONFINITE 1
+#define UD_TI_ST_BOXES 2
+#define UD_TI_ST_RANGE 4
+#define UD_TI_ST_KEY 8
+#define UD_TI_ST_DUPLICATE 16
+
+typedef struct {
+  int num_classes;
+  int mode;                 /* UD_TI_MODE_* */
+  int max_boxes_per_sample;
+  int max_frame_rows;       /* the most GT rows, or prediction rows, of one sample */
+  int64_t num_rows, num_gt, num_samples, num_frames, num_scenes;
+  int64_t max_scene_rows;   /* the most prediction rows of one scene: prediction keys lie in 1 .. max_scene_rows */
+  int64_t max_gt_keys;      /* GT keys lie in 0 .. max_gt_keys - 1 */
+  int64_t num_out_pred, num_out_gt; /* rows of the two outputs: 0 for the count call */
+  double class_range[UD_NUS_MAX_CLASSES];
+  uint8_t track_class[UD_NUS_MAX_CLASSES + 1]; /* non-zero: the class is tracked */
+} UdTrackInterpCfg;
+
+size_t ud_track_interp_workspace_bytes(const UdTrackInterpCfg* cfg);
+int ud_track_interp_count(const double* pred_rec, const int32_t* pred_cls, const int32_t* track_id, const int64_t* row_start,
+                          const int64_t* row_count, const double* gt_xyz, const int32_t* gt_cls, const int32_t* gt_num_pts,
+                          const uint8_t* gt_keep, const int32_t* gt_key, const int64_t* gt_off, const double* ego,
+                          const int64_t* frame_sample, const int64_t* scene_off, const int64_t* frame_ts,
+                          const UdTrackInterpCfg* cfg_host, int64_t* counts, int32_t* status, void* workspace,
+                          size_t workspace_bytes, ud_stream_t stream);
+int ud_track_interp_fill(const double* pred_rec, const int32_t* pred_cls, const int32_t* track_id, const int64_t* row_start,
+                         const int64_t* row_count, const double* gt_xyz, const int32_t* gt_cls, const int32_t* gt_num_pts,
+                         const uint8_t* gt_keep, const int32_t* gt_key, const int64_t* gt_off, const double* ego,
+                         const int64_t* frame_sample, const int64_t* scene_off, const int64_t* frame_ts,
+                         const UdTrackInterpCfg* cfg_host, const int64_t* pred_out_start, const int64_t* pred_out_count,
+                         const int64_t* gt_out_start, const int64_t* gt_out_count, double* out_rec, int32_t* out_pred_cls,
+                         int32_t* out_pred_key, int32_t* out_pred_src, double* out_xyz, int32_t* out_gt_cls,
+                         int32_t* out_gt_key, int32_t* out_gt_src, int32_t* status, void* workspace, size_t workspace_bytes,
+                         ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
