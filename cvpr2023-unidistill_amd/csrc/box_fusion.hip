@@ -23,23 +23,24 @@
 // Output: per sample the clusters by fused (fp32) score descending, ties by anchor order, at most max_out; zero padded.
 //
 //   k_bf_gather : one workgroup per sample: validity, ordered compaction, (label, score, position) keys, bitonic sort in
-//                 LDS, then the un-viewed boxes written in sorted order.
-//   k_bf_mask   : one thread per (box i, word of 64 later boxes): suppression bits of the same-label pairs only -- the order
-//                 is label-major, so the mask is block-diagonal and words past the label's run cost one compare.
-//   k_bf_fuse   : one workgroup per sample: wave 0 runs nms.hip's one-wave scan and records each box's anchor; then one
-//                 thread per anchor walks its mask row and accumulates its members; then the clusters are sorted by fused
-//                 score in LDS and the first max_out are written.
+//                 LDS (lds_sort.h), then the un-viewed boxes written in sorted order.
+//   k_bf_mask   : one thread per (box i, word of 64 later boxes): suppression bits of the same-label pairs only (nms_scan.h:
+//                 ud_nms_mask_word with the labels) -- the order is label-major, so the mask is block-diagonal and words past
+//                 the label's run cost one compare.
+//   k_bf_fuse   : one workgroup per sample: wave 0 runs the one-wave NMS scan (nms_scan.h: ud_nms_scan, the scan of nms.hip)
+//                 and records each box's anchor from the freshly removed bits; then one thread per anchor walks its mask row
+//                 and accumulates its members; then the clusters are sorted by fused score in LDS and the first max_out are
+//                 written.
 #include "ud_common.h"
 #include "ud_prof.h"
-#include "bev_iou.h"
+#include "lds_sort.h"
+#include "nms_scan.h"
 #include <cmath>
 
 namespace {
 
-using ud_iou::iou_bev;
-
 constexpr int kMaxSources = 16;
-constexpr int kMaxBoxes = 64 * 64 * 4;      // 16384 valid boxes per sample: the NMS scan's limit
+constexpr int kMaxBoxes = ud_nms_scan_capacity(kNmsWordsPerLane);      // 16384 valid boxes per sample: the NMS scan's limit
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr double kPi = 3.14159265358979323846;
@@ -52,28 +53,6 @@ struct Source {
 struct Sources {
   Source s[kMaxSources];
 };
-
-// ascending sort of n (a power of two) keys in LDS by the whole workgroup
-__device__ __forceinline__ void bitonic_sort(unsigned long long* key, int n) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n; i += kThreads) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long a = key[i], c = key[p];
-          if ((a > c) == ((i & k) == 0)) { key[i] = c; key[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// fp32 -> 32 bits that ascend as the float descends (-0 was made +0 by the caller)
-__device__ __forceinline__ unsigned descending_bits(float v) {
-  const unsigned u = __float_as_uint(v);
-  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
 
 __device__ __forceinline__ void unview(const Source& v, const float* in, int box_dim, double* u) {
   const double fx = v.fx ? -1.0 : 1.0, fy = v.fy ? -1.0 : 1.0;
@@ -102,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void k_bf_gather(
     double* __restrict__ sweight, int* __restrict__ slabel, int* __restrict__ ssrc, int* __restrict__ nvalid) {
   extern __shared__ unsigned long long s_key[];
   __shared__ int s_wsum[kWaves];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int total = S * R;
   int base = 0;
   for (int t0 = 0; t0 < total; t0 += kThreads) {
@@ -122,24 +101,15 @@ __global__ __launch_bounds__(kThreads) void k_bf_gather(
         for (int k = 0; k < box_dim; ++k) ok = ok && isfinite(p[k]);
       }
     }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) s_wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int c = s_wsum[w];
-      before += w < wave ? c : 0;
-      all += c;
-    }
-    const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+    const UdBlockRank cr = ud_block_rank<kWaves>(ok, s_wsum);
+    const int pos = base + cr.rank();
     if (ok && pos < cap) {
-      s_key[pos] = ((unsigned long long)label << 48) | ((unsigned long long)descending_bits(score + 0.0f) << 16) |
+      s_key[pos] = ((unsigned long long)label << 48) | ((unsigned long long)ud_desc_bits(score + 0.0f) << 16) |
                    (unsigned long long)pos;
       slot[(size_t)b * cap + pos] = t;
     }
-    base += all;
-    __syncthreads();
+    base += cr.total;
+    __syncthreads();                                   // s_wsum is read: the next trip may write it
   }
   // more valid boxes than the scan can hold (possible only when S * R > 16384): the sample is reported, not fused
   const bool overflow = base > kMaxBoxes;
@@ -148,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void k_bf_gather(
   for (int i = tid; i < npow2; i += kThreads)
     if (i >= n) s_key[i] = kPadKey;
   __syncthreads();
-  bitonic_sort(s_key, npow2);
+  ud_bitonic_sort<kThreads>(s_key, npow2);
   for (int i = tid; i < n; i += kThreads) {
     const unsigned long long key = s_key[i];
     const size_t o = (size_t)b * cap + i;
@@ -178,61 +148,9 @@ __global__ __launch_bounds__(256) void k_bf_mask(const float* __restrict__ sboxf
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   const int i = (int)(t / words), wj = (int)(t - (long long)i * words);
   if (i >= n || wj >= nwords) return;
-  const float* boxes = sboxf + (size_t)b * cap * 7;
-  const int* lab = slabel + (size_t)b * cap;
-  unsigned long long bits = 0ull;
-  const int j0 = wj * 64, jbeg = max(j0, i + 1), jend = min(j0 + 64, n);
-  if (jbeg < jend) {
-    const int li = lab[i];
-    if (lab[jbeg] == li) {                           // labels ascend: past the label's run nothing is suppressed
-      float bi[7];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) bi[k] = boxes[(size_t)i * 7 + k];
-      for (int j = jbeg; j < jend; ++j) {
-        if (lab[j] != li) break;
-        float bj[7];
-#pragma unroll
-        for (int k = 0; k < 7; ++k) bj[k] = boxes[(size_t)j * 7 + k];
-        if (iou_bev(bi, bj) > thresh) bits |= 1ull << (j - j0);
-      }
-    }
-  }
-  mask[((size_t)b * cap + i) * words + wj] = bits;
-}
-
-// k_nms_reduce's scan by one wave, recording for every box the anchor that took it (itself for a kept box)
-__device__ __forceinline__ void scan_anchors(const unsigned long long* __restrict__ mask, int n, int words,
-                                             int* __restrict__ anchor, int lane) {
-  constexpr int kWordsPerLane = 4;
-  const int nwords = (n + 63) >> 6;
-  unsigned long long removed[kWordsPerLane] = {0ull, 0ull, 0ull, 0ull};
-  for (int i = 0; i < n; ++i) {
-    const int w = i >> 6, owner = w & 63, sl = w >> 6;
-    unsigned long long word = 0ull;
-#pragma unroll
-    for (int s = 0; s < kWordsPerLane; ++s)
-      if (s == sl) word = removed[s];
-    const unsigned lo = __shfl((unsigned)(word & 0xFFFFFFFFull), owner);
-    const unsigned hi = __shfl((unsigned)(word >> 32), owner);
-    const unsigned long long cur = ((unsigned long long)hi << 32) | lo;
-    if (!((cur >> (i & 63)) & 1ull)) {              // wave-uniform
-      if (lane == 0) anchor[i] = i;
-#pragma unroll
-      for (int s = 0; s < kWordsPerLane; ++s) {
-        const int wj = lane + 64 * s;
-        if (wj < nwords) {
-          const unsigned long long row = mask[(size_t)i * words + wj];
-          unsigned long long fresh = row & ~removed[s];
-          removed[s] |= row;
-          while (fresh) {
-            const int bit = __ffsll((long long)fresh) - 1;
-            anchor[wj * 64 + bit] = i;
-            fresh &= fresh - 1ull;
-          }
-        }
-      }
-    }
-  }
+  // labels ascend: past the label's run nothing is suppressed
+  mask[((size_t)b * cap + i) * words + wj] =
+      ud_nms_mask_word<true>(sboxf + (size_t)b * cap * 7, 7, i, wj, n, thresh, slabel + (size_t)b * cap);
 }
 
 __global__ __launch_bounds__(kThreads) void k_bf_fuse(
@@ -249,7 +167,15 @@ __global__ __launch_bounds__(kThreads) void k_bf_fuse(
   const size_t o0 = (size_t)b * cap;
   mask += o0 * words;
   anchor += o0;
-  if (tid < 64) scan_anchors(mask, n, words, anchor, tid);
+  if (tid < 64)                     // the NMS scan, recording for every box the anchor that took it (itself for a kept box)
+    ud_nms_scan<kNmsWordsPerLane>(
+        mask, n, nwords, words, n, [&](int i, int) { if (tid == 0) anchor[i] = i; },
+        [&](int i, int wj, unsigned long long fresh) {
+          while (fresh) {
+            anchor[wj * 64 + __ffsll((long long)fresh) - 1] = i;
+            fresh &= fresh - 1ull;
+          }
+        });
   if (tid == 0) s_count = 0;
   __syncthreads();
   for (int i = tid; i < npow2; i += kThreads) {
@@ -290,12 +216,12 @@ __global__ __launch_bounds__(kThreads) void k_bf_fuse(
       const float sc = (float)(csum / fmax(wsum, wsum_all));
       fscore[o0 + i] = sc;
       fcount[o0 + i] = members;
-      key = ((unsigned long long)descending_bits(sc + 0.0f) << 32) | (unsigned long long)i;
+      key = ((unsigned long long)ud_desc_bits(sc + 0.0f) << 32) | (unsigned long long)i;
     }
     s_key[i] = key;
   }
   __syncthreads();
-  bitonic_sort(s_key, npow2);
+  ud_bitonic_sort<kThreads>(s_key, npow2);
   for (int i = tid; i < npow2; i += kThreads)                     // clusters sort before the padding: their count
     if (s_key[i] != kPadKey && (i + 1 == npow2 || s_key[i + 1] == kPadKey)) s_count = i + 1;
   __syncthreads();

@@ -139,12 +139,6 @@ __device__ __forceinline__ double dm_wave_sum_d(double v) {
   return v;
 }
 
-__device__ __forceinline__ int dm_wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-
 // Channels-last (sc == 1): a wave per pixel reads its D logits as one contiguous row, lane l holding bins l, l + 64, ...;
 // the four waves of a workgroup take 16 pixels each of the slice.
 __global__ __launch_bounds__(256) void k_depth_metric_cl(const float* __restrict__ x, long long sn, long long sh, long long sw,
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(256) void k_depth_metric_cl(const float* __restrict
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) sum64 += (double)e[s];
-        ahat = dm_wave_min_i(ahat);
+        ahat = ud_wave_min(ahat);
         if (ahat >= D) ahat = 0;                     // no bin compares equal (NaN logits): what the lane-per-pixel walk gives
         const float sum = (float)dm_wave_sum_d(sum64);
         float pbl = 0.f;

@@ -9,12 +9,13 @@
 // four half-planes of rectangle B, shoelace area; IoU = inter / max(area_a + area_b - inter, 1e-8).
 //
 //   k_nms_mask   : one thread per (box i, block of 64 later boxes) -> 64 suppression bits
-//   k_nms_reduce : ONE wave walks the boxes in score order (the inherently sequential part, kept on
-//                  the device so the proposal layer never synchronises with the host): lane w owns
-//                  word w of the running "removed" bitmap; keep list and count are written out.
+//                  (nms_scan.h: ud_nms_mask_word)
+//   k_nms_reduce : ONE wave walks the boxes in score order (nms_scan.h: ud_nms_scan; the inherently
+//                  sequential part, kept on the device so the proposal layer never synchronises with
+//                  the host); keep list and count are written out.
 #include "ud_common.h"
 #include "ud_prof.h"
-#include "bev_iou.h"
+#include "nms_scan.h"
 
 namespace {
 
@@ -25,51 +26,16 @@ __global__ __launch_bounds__(256) void k_nms_mask(const float* __restrict__ boxe
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long long)N * words) return;
   const int i = (int)(t / words), wj = (int)(t - (long long)i * words);
-  unsigned long long bits = 0ull;
-  const int j0 = wj * 64;
-  if (j0 + 63 > i) {                              // only later boxes can be suppressed by i
-    float bi[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) bi[k] = boxes[(size_t)i * 7 + k];
-    for (int jj = 0; jj < 64; ++jj) {
-      const int j = j0 + jj;
-      if (j <= i || j >= N) continue;
-      float bj[7];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) bj[k] = boxes[(size_t)j * 7 + k];
-      if (iou_bev(bi, bj) > thresh) bits |= 1ull << jj;
-    }
-  }
-  mask[(size_t)i * words + wj] = bits;
+  mask[(size_t)i * words + wj] = ud_nms_mask_word(boxes, 7, i, wj, N, thresh);
 }
 
 __global__ __launch_bounds__(64) void k_nms_reduce(const unsigned long long* __restrict__ mask, int N,
                                                    int words, long long* __restrict__ keep,
                                                    int* __restrict__ num_keep) {
   const int lane = threadIdx.x;
-  // lane w owns removed-bitmap words w, w + 64, ... (N <= 64 * 64 * kWordsPerLane)
-  constexpr int kWordsPerLane = 4;
-  unsigned long long removed[kWordsPerLane] = {0ull, 0ull, 0ull, 0ull};
-  int count = 0;
-  for (int i = 0; i < N; ++i) {
-    const int w = i >> 6, owner = w & 63, slot = w >> 6;
-    unsigned long long word = 0ull;
-#pragma unroll
-    for (int s = 0; s < kWordsPerLane; ++s)
-      if (s == slot) word = removed[s];
-    const unsigned lo = __shfl((unsigned)(word & 0xFFFFFFFFull), owner);
-    const unsigned hi = __shfl((unsigned)(word >> 32), owner);
-    const unsigned long long cur = ((unsigned long long)hi << 32) | lo;
-    if (!((cur >> (i & 63)) & 1ull)) {            // wave-uniform
-      if (lane == 0) keep[count] = i;
-      ++count;
-#pragma unroll
-      for (int s = 0; s < kWordsPerLane; ++s) {
-        const int wj = lane + 64 * s;
-        if (wj < words) removed[s] |= mask[(size_t)i * words + wj];
-      }
-    }
-  }
+  const int count = ud_nms_scan<kNmsWordsPerLane>(
+      mask, N, words, words, N, [&](int i, int k) { if (lane == 0) keep[k] = i; },
+      [](int, int, unsigned long long) {});
   if (lane == 0) *num_keep = count;
   for (int k = count + lane; k < N; k += 64) keep[k] = -1;
 }
@@ -86,7 +52,7 @@ __global__ __launch_bounds__(256) void k_iou_matrix(const float* __restrict__ a,
   iou[t] = iou_bev(ba, bb);
 }
 
-constexpr int kMaxBoxes = 64 * 64 * 4;   // 16384
+constexpr int kMaxBoxes = ud_nms_scan_capacity(kNmsWordsPerLane);   // 16384
 
 }  // namespace
 

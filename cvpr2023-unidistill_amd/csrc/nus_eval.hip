@@ -15,6 +15,7 @@
 // Float64 throughout, no contraction (-ffp-contract=off): every expression is evaluated as the oracle writes it.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "lds_sort.h"
 #include "radix_sort.h"
 
 namespace {
@@ -24,18 +25,6 @@ constexpr int kCols = UD_NUS_PRED_COLS, kGtCols = UD_NUS_GT_COLS, kPts = UD_NUS_
 constexpr int kErrs = 5;
 constexpr int kSortBits = 36;                 // 4 class bits above 32 score bits
 constexpr double kPi = 3.141592653589793;     // numpy.pi
-
-__device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
-
-// descending order of a float32 score as an ascending 32-bit key
-__device__ __forceinline__ unsigned desc_score_key(double score) {
-  const unsigned b = __float_as_uint((float)score);
-  const unsigned asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ~asc;
-}
 
 struct AttrTab {
   int moving[UD_NUS_MAX_CLASSES], still[UD_NUS_MAX_CLASSES];   // attribute id per class when speed > 0.2 / otherwise
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(256) void k_nus_match(UdNusCfg cfg, UdNusEvalIo io,
     const int c = io.gt_cls[g0 + j];
     bool keep = false;
     if (c >= 0 && c < C) {
-      keep = io.gt_keep[g0 + j] != 0 && io.gt_num_pts[g0 + j] != 0 && dist2d(g[0], g[1], ex, ey) < cfg.class_range[c];
+      keep = io.gt_keep[g0 + j] != 0 && io.gt_num_pts[g0 + j] != 0 && ud_dist_xy(g[0], g[1], ex, ey) < cfg.class_range[c];
     } else {
       atomicOr(io.status, UD_NUS_ST_CLASS);
     }
@@ -131,8 +120,8 @@ __global__ __launch_bounds__(256) void k_nus_match(UdNusCfg cfg, UdNusEvalIo io,
   for (int i = tid; i < np_; i += 256) {
     const double* p = io.pred_rec + (p0 + i) * kCols;
     const int c = io.pred_cls[p0 + i];
-    const bool keep = c >= 0 && c < C && dist2d(p[0], p[1], ex, ey) < cfg.class_range[c];
-    const unsigned desc = desc_score_key(p[9]);
+    const bool keep = c >= 0 && c < C && ud_dist_xy(p[0], p[1], ex, ey) < cfg.class_range[c];
+    const unsigned desc = ud_desc_bits((float)p[9]);
     s_key[i] = keep ? ((unsigned long long)c << 42) | ((unsigned long long)desc << 10) | (unsigned)(kMaxBoxes - 1 - i)
                     : (15ull << 42) | (unsigned)i;
     const int64_t q = q0 + i;
@@ -173,7 +162,7 @@ __global__ __launch_bounds__(256) void k_nus_match(UdNusCfg cfg, UdNusEvalIo io,
     for (int k = 0; k < nchunk; ++k) {                   // first minimum of the lane's GT (ascending index)
       const int j = k * 64 + lane;
       if (j < ng && s_gc[j] == c && !((taken >> k) & 1u)) {
-        const double d = dist2d(px, py, s_gx[j], s_gy[j]);
+        const double d = ud_dist_xy(px, py, s_gx[j], s_gy[j]);
         if (d < bd) bd = d, bj = j;
       }
     }

@@ -12,20 +12,21 @@
 //       top-K of the nc*H*W sigmoid scores == the reference's per-class top-K followed by the top-K of
 //       their union.  Keys are 64 bit, (score bits << 32) | ~flat index, hence unique: an LDS radix select
 //       (8-bit digits from the top, stops as soon as the K-th key is isolated) finds the K-th key, the keys
-//       above it are compacted and bitonic-sorted in LDS: descending score, ascending (class, pixel) on equal
-//       scores.  Each thread then decodes its ranks in registers (same fp32 operations in the same order as
+//       above it are compacted and bitonic-sorted in LDS (lds_sort.h): descending score, ascending (class, pixel)
+//       on equal scores.  Each thread then decodes its ranks in registers (same fp32 operations in the same order as
 //       the reference's tensor code), applies the centre-range and score masks, and the survivors are
 //       sorted by the NMS score (descending, rank order on ties) into box rows [x y z dx dy dz rot (vx vy)
 //       score label] + a device count.
 //   k_prop_mask   : 64 suppression bits per (box i, word of later boxes) of every (sample, task), bounded by
-//       the device counts (csrc/bev_iou.h: the IoU of nms.hip).
-//   k_prop_select : one workgroup per sample, wave t walks task t's boxes in NMS-score order (the inherently
-//       sequential part) up to post_max keepers; the tasks' keepers are then packed back to back into
+//       the device counts (nms_scan.h: ud_nms_mask_word, the mask word of nms.hip).
+//   k_prop_select : one workgroup per sample, wave t walks task t's boxes in NMS-score order (nms_scan.h:
+//       ud_nms_scan with one mask word per lane) up to post_max keepers; the tasks' keepers are then packed back to back into
 //       rois / roi_scores / roi_labels (zero padded, labels = 1 + class offset of the task + class), and the
 //       per-sample total is written: the ONE number the host reads to slice pred_dicts.
 #include "ud_common.h"
 #include "ud_prof.h"
-#include "bev_iou.h"
+#include "lds_sort.h"
+#include "nms_scan.h"
 
 namespace {
 
@@ -34,6 +35,7 @@ constexpr int kMaxK = 2048;          // top-K candidates per (sample, task): LDS
 constexpr int kMaxPost = 512;        // kept boxes per task
 constexpr int kRow = 11;             // floats per sorted candidate row: 9 box values, score, label
 constexpr int kThreads = 1024;
+static_assert(kMaxK <= ud_nms_scan_capacity(1), "k_prop_select scans with one mask word per lane");
 
 struct Desc {                        // one head tensor [B, c, H*W] through its strides (elements)
   const float* p;
@@ -59,22 +61,6 @@ __device__ __forceinline__ unsigned long long score_key(const Task& tk, int b, i
   const int c = i / HW, pix = i - c * HW;
   const float s = 1.0f / (1.0f + expf(-ld(tk.d[0], b, c, pix)));       // torch.sigmoid
   return ((unsigned long long)__float_as_uint(s) << 32) | (unsigned)(~(unsigned)i);
-}
-
-// descending bitonic sort of n (power of two) 64-bit keys in LDS by the whole workgroup
-__device__ __forceinline__ void bitonic_desc(unsigned long long* keys, int n) {
-  for (int k = 2; k <= n; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n; i += kThreads) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long a = keys[i], b = keys[p];
-          const bool desc = (i & k) == 0;
-          if (desc ? (a < b) : (a > b)) { keys[i] = b; keys[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_prop_decode(Params P, float* __restrict__ rows,
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void k_prop_decode(Params P, float* __res
     }
   }
   __syncthreads();
-  bitonic_desc(keys, n2);
+  ud_bitonic_sort<kThreads, true>(keys, n2);          // descending: the padding's key 0 sorts last
 
   // ---- decode my ranks in registers -------------------------------------------------------------
   constexpr int kPer = kMaxK / kThreads;
@@ -199,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void k_prop_decode(Params P, float* __res
     if (r < n2) keys[r] = key2[q];
   }
   __syncthreads();
-  bitonic_desc(keys, n2);
+  ud_bitonic_sort<kThreads, true>(keys, n2);          // descending: a masked rank's key 0 sorts last
   for (int j = tid; j < n2; j += kThreads) {
     const unsigned long long k2 = keys[j];
     if (k2 != 0ull) pos_of_rank[(int)(~(unsigned)k2)] = j;
@@ -226,23 +212,7 @@ __global__ __launch_bounds__(256) void k_prop_mask(const float* __restrict__ row
   const long long tt = (long long)blockIdx.x * 256 + threadIdx.x;
   if (tt >= (long long)N * words) return;
   const int i = (int)(tt / words), wj = (int)(tt - (long long)i * words);
-  const float* boxes = rows + (size_t)bt * K * kRow;
-  unsigned long long bits = 0ull;
-  const int j0 = wj * 64;
-  if (j0 + 63 > i && j0 < N) {
-    float bi[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) bi[k] = boxes[(size_t)i * kRow + k];
-    for (int jj = 0; jj < 64; ++jj) {
-      const int j = j0 + jj;
-      if (j <= i || j >= N) continue;
-      float bj[7];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) bj[k] = boxes[(size_t)j * kRow + k];
-      if (ud_iou::iou_bev(bi, bj) > thresh) bits |= 1ull << jj;
-    }
-  }
-  mask[((size_t)bt * K + i) * words + wj] = bits;
+  mask[((size_t)bt * K + i) * words + wj] = ud_nms_mask_word(rows + (size_t)bt * K * kRow, kRow, i, wj, N, thresh);
 }
 
 __global__ __launch_bounds__(64 * kMaxTasks) void k_prop_select(
@@ -255,19 +225,9 @@ __global__ __launch_bounds__(64 * kMaxTasks) void k_prop_select(
   if (wave < P.T) {
     const int bt = b * P.T + wave, N = counts[bt];
     const unsigned long long* m = mask + (size_t)bt * P.K * words;
-    unsigned long long removed = 0ull;             // lane w owns word w (words <= 32)
-    int count = 0;
-    for (int i = 0; i < N && count < P.post_max; ++i) {
-      const int w = i >> 6;
-      const unsigned lo = __shfl((unsigned)(removed & 0xFFFFFFFFull), w);
-      const unsigned hi = __shfl((unsigned)(removed >> 32), w);
-      const unsigned long long cur = ((unsigned long long)hi << 32) | lo;
-      if (!((cur >> (i & 63)) & 1ull)) {           // wave-uniform
-        if (lane == 0) keep[wave][count] = (short)i;
-        ++count;
-        if (lane < words) removed |= m[(size_t)i * words + lane];
-      }
-    }
+    const int count = ud_nms_scan<1>(                // lane w owns word w (words <= 32)
+        m, N, words, words, P.post_max, [&](int i, int k) { if (lane == 0) keep[wave][k] = (short)i; },
+        [](int, int, unsigned long long) {});
     if (lane == 0) kept[wave] = count;
   }
   __syncthreads();

@@ -2,11 +2,13 @@
 // association over the evaluator's global-frame rows, all scenes in ONE launch.
 //
 //   k_track_scenes : one 1024-thread workgroup per scene, the scene's frames walked in order inside it.  Per frame:
-//     A  one thread per row: the candidate test, ordered compaction, (descending score, row) keys, a bitonic sort of (key, row)
-//        pairs in LDS (the row in the high bits of the second word, so equal scores order by row whatever the classes); the live tracks coast (ct += v * dt) in the same phase;
+//     A  the live tracks coast (ct += v * dt); one thread per row: the candidate test, ordered compaction, (descending score,
+//        row) keys, a bitonic sort of (key, row) pairs in LDS (lds_sort.h; the row in the high bits of the second word, so
+//        equal scores order by row whatever the classes);
 //     B  one wave per class: the class's candidates in order; per candidate the 64 lanes scan the live tracks of that class
-//        (d2 = dx * dx + dy * dy, no square root), a lexicographic (d2, slot) minimum across the wave, the accept test, and
-//        the owner lane of the winning slot retires it.  Classes never share a track, so the waves do not interact;
+//        (d2 = dx * dx + dy * dy, no square root), a lexicographic (d2, slot) minimum across the wave (ud_wave_min_pair), the
+//        accept test, and the owner lane of the winning slot retires it.  Classes never share a track, so the waves do not
+//        interact;
 //     C  one thread per candidate: the matched track's id and hits (or the next ids, by a prefix count of the unmatched),
 //        barrier, then the new generation and the two outputs are written.
 //
@@ -17,13 +19,14 @@
 // "Lowest slot" is "lowest (age, position)", which is the order the lanes scan in.
 //
 // LDS (dynamic, by max_age; 160 KiB per CU): centres 2 x f64 and class u8 per slot (17 B x max_age x 1024), the frame's keys
-// u64[1024], rows and matches i32[1024] each: 67 KiB at max_age 3, 152 KiB at max_age 8; one workgroup per CU either way (74
+// u64[1024], rows and matches i32[1024] each: 67 KiB at max_age 3, 152 KiB at max_age 8; one workgroup per CU either way (76
 // VGPRs at 16 waves per workgroup).  Velocity, id and hits are touched once per frame and live in the scene's slice of the
 // workspace (24 B per slot).
 //
 // No inter-workgroup communication, no spinning, no floating-point atomics; the only atomic is the OR into *status.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "lds_sort.h"
 #include <cmath>
 
 namespace {
@@ -52,28 +55,6 @@ __host__ __device__ inline size_t lds_bytes(int max_age) {
 
 // the workspace slice of one scene: vx[cap] vy[cap] f64, id[cap] hits[cap] i32, cap = max_age * kGen
 __host__ __device__ inline size_t scene_bytes(int max_age) { return (size_t)max_age * kGen * 24; }
-
-// ascending sort of n (a power of two) (key, row) pairs in LDS by the whole workgroup
-__device__ __forceinline__ void bitonic_sort_pairs(unsigned long long* key, int* val, int n) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int i = threadIdx.x, p = i ^ j;
-      if (i < n && p > i) {
-        const unsigned long long a = key[i], c = key[p];
-        const int va = val[i], vc = val[p];
-        const bool gt = a > c || (a == c && va > vc);
-        if (gt == ((i & k) == 0)) { key[i] = c; key[p] = a; val[i] = vc; val[p] = va; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// f64 -> 64 bits that ascend as the value descends (-0 was made +0 by the caller)
-__device__ __forceinline__ unsigned long long descending_bits(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return ~((u >> 63) ? ~u : (u | 0x8000000000000000ull));
-}
 
 __global__ __launch_bounds__(kThreads) void k_track_scenes(
     const double* __restrict__ rec, const int* __restrict__ cls, const long long* __restrict__ row_start,
@@ -134,8 +115,6 @@ __global__ __launch_bounds__(kThreads) void k_track_scenes(
         ok = finite && score >= prm.score_threshold;
       }
     }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) s_wsum[wave] = __popcll(bal);
     for (int slot = tid; slot < cap; slot += kThreads) {
       const int g = slot / kGen;
       if ((slot - g * kGen) < s_ngen[g] && s_cls[slot] != kDead) {
@@ -143,24 +122,19 @@ __global__ __launch_bounds__(kThreads) void k_track_scenes(
         s_cty[slot] = s_cty[slot] + w_vy[slot] * dt;
       }
     }
-    __syncthreads();
-    int before = 0, ncand = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int n = s_wsum[w];
-      before += w < wave ? n : 0;
-      ncand += n;
-    }
+    const UdBlockRank cr = ud_block_rank<kWaves>(ok, s_wsum);          // its barrier also stands behind the coast
+    const int ncand = cr.total;
     int npow2 = 1;
     while (npow2 < ncand) npow2 <<= 1;
     if (ok) {
-      const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
-      s_key[pos] = descending_bits(score + 0.0);
+      const int pos = cr.rank();
+      s_key[pos] = ud_desc_bits(score + 0.0);
       s_row[pos] = (tid << kClsBits) | c;
     }
     if (tid >= ncand && tid < npow2) { s_key[tid] = kPadKey; s_row[tid] = 0x7FFFFFFF; }
     __syncthreads();
-    bitonic_sort_pairs(s_key, s_row, npow2);
+    __builtin_assume(npow2 <= kThreads);                               // one element per thread: the sort's loop runs once
+    ud_bitonic_sort<kThreads>(s_key, s_row, npow2);
 
     // ---- B: greedy match, one wave per class
     if (wave < prm.num_classes && prm.track_class[wave]) {
@@ -188,12 +162,7 @@ __global__ __launch_bounds__(kThreads) void k_track_scenes(
               }
             }
           }
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            const double od = __shfl_xor(best, o);
-            const int os = __shfl_xor(bslot, o);
-            if (od < best || (od == best && os < bslot)) { best = od; bslot = os; }
-          }
+          ud_wave_min_pair(best, bslot);
           const bool hit = bslot != 0x7FFFFFFF && best <= md2;
           if (hit) {
             const int a = bslot / kGen, p = bslot - a * kGen;
@@ -218,18 +187,9 @@ __global__ __launch_bounds__(kThreads) void k_track_scenes(
         hits = a == 0 ? w_hits[g * kGen + p] + 1 : 1;                  // a rematch after a miss restarts at 1
       }
     }
-    const unsigned long long fresh = __ballot(cand && m < 0);
-    if (lane == 0) s_wsum[wave] = __popcll(fresh);
-    __syncthreads();                                                   // also: every read of the old generation is done
-    int fbefore = 0, nfresh = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int n = s_wsum[w];
-      fbefore += w < wave ? n : 0;
-      nfresh += n;
-    }
+    const UdBlockRank fr = ud_block_rank<kWaves>(cand && m < 0, s_wsum);   // its barrier: every read of the old generation is done
     if (cand) {
-      if (m < 0) id = next_id + fbefore + __popcll(fresh & ((1ull << lane) - 1ull)) + 1;
+      if (m < 0) id = next_id + fr.rank() + 1;
       const int packed = s_row[tid];
       const long long row = start + (packed >> kClsBits);
       const double* r = rec + row * UD_NUS_PRED_COLS;
@@ -245,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void k_track_scenes(
       track_hits[row] = hits;
     }
     if (tid == 0) s_ngen[fno] = ncand;
-    next_id += nfresh;
+    next_id += fr.total;
     __syncthreads();
   }
   if (st) atomicOr(status, st);

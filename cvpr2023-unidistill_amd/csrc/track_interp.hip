@@ -9,12 +9,14 @@
 //                      per sample = kept + interpolated, the interpolated total, the GT rows per class.
 //   k_ti_walk<true>  : fill call.  The same walk; the thread that closes a hole leaves one entry (key, L row, R row, L frame, R
 //                      frame) per frame of the hole, in the order the integer atomics happen to give.
-//   k_ti_emit        : fill call.  One workgroup per (frame, side): the kept rows compacted in row order, then the frame's entries
-//                      ranked by key (unique within a frame), each interpolated row computed by one thread from its two endpoints.
+//   k_ti_emit        : fill call.  One workgroup per (frame, side): the kept rows compacted in row order (lds_sort.h), then the
+//                      frame's entries ranked by key (unique within a frame), each interpolated row computed by one thread from
+//                      its two endpoints.
 //
 // No floating-point atomics, no inter-workgroup communication, nothing waits on the host inside a call.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "lds_sort.h"
 #include "track_kept.h"
 #include <climits>
 #include <cmath>
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_ti_emit(Params prm) {
   __shared__ int s_key[kThreads];
   __shared__ int s_wsum[kWaves];
   const Side& sd = prm.side[blockIdx.y];
-  const int tid = threadIdx.x, lane = tid & (UD_WAVE - 1), wave = tid / UD_WAVE;
+  const int tid = threadIdx.x;
   const long long fi = blockIdx.x;
   int st = 0;
   long long sample, r0;
@@ -200,17 +202,10 @@ __global__ __launch_bounds__(kThreads) void k_ti_emit(Params prm) {
   int key = 0, c = 0;
   const long long row = r0 + tid;
   if (tid < rn) kept = side_kept(prm, sd, row, sample, key, c, st);
-  const unsigned long long bal = __ballot(kept);
-  if (lane == 0) s_wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int before = 0, nkept = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    before += w < wave ? s_wsum[w] : 0;
-    nkept += s_wsum[w];
-  }
+  const UdBlockRank cr = ud_block_rank<kWaves>(kept, s_wsum);
+  const int nkept = cr.total;
   if (kept) {
-    const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+    const int pos = cr.rank();
     if (pos < on) {
       const double* v = sd.vals + row * sd.cols;
       double* o = sd.out_vals + (o0 + pos) * sd.cols;

@@ -16,6 +16,5 @@ __device__ __forceinline__ bool ud_tm_row_kept(bool candidate, int c, int num_cl
     st |= nonfinite_bit;
     return false;
   }
-  const double dx = vals[0] - ego[0], dy = vals[1] - ego[1];
-  return sqrt(dx * dx + dy * dy) <= range[c];
+  return ud_dist_xy(vals[0], vals[1], ego[0], ego[1]) <= range[c];
 }

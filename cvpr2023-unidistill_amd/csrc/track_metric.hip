@@ -16,6 +16,7 @@
 // waits on the host: the launches above are enqueued back to back.
 #include "ud_common.h"
 #include "ud_prof.h"
+#include "lds_sort.h"
 #include "radix_sort.h"
 #include <cmath>
 
@@ -79,17 +80,6 @@ __host__ __device__ inline size_t walk_lds_bytes(int cap, int ic) {
 
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
-__device__ __forceinline__ double dist_xy(double ax, double ay, double bx, double by) {
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
-
-// f64 -> 64 bits that ascend as the value descends (-0 was made +0 by the caller)
-__device__ __forceinline__ unsigned long long descending_bits(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return ~((u >> 63) ? ~u : (u | 0x8000000000000000ull));
-}
-
 // a frame's sample and its two row ranges, checked against the inputs; false: the frame is treated as empty
 __device__ __forceinline__ bool frame_rows(const Ptrs& a, const Params& prm, long long fi, int cap, long long& sample,
                                            long long& g0, int& gn, long long& p0, int& pn, int& st) {
@@ -137,7 +127,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_tm_scores(Ptrs a, Params prm)
         if (!finite3(r[0], r[1], r[2]) || !isfinite(score)) {
           st |= UD_TM_ST_NONFINITE;
         } else {
-          kept = dist_xy(r[0], r[1], a.ego[sample * 3], a.ego[sample * 3 + 1]) <= prm.range[c];
+          kept = ud_dist_xy(r[0], r[1], a.ego[sample * 3], a.ego[sample * 3 + 1]) <= prm.range[c];
           if (kept && id >= prm.slots) { st |= UD_TM_ST_ID; kept = false; }
         }
       }
@@ -178,25 +168,6 @@ __global__ __launch_bounds__(kScoreThreads) void k_tm_scores(Ptrs a, Params prm)
 }
 
 // ---- the walk ----------------------------------------------------------------------------------------------------------------------
-struct WaveMin {
-  double v;
-  int j;
-};
-__device__ __forceinline__ WaveMin wave_min_pair(double v, int j) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oj = __shfl_xor(j, o);
-    if (ov < v || (ov == v && oj < j)) { v = ov; j = oj; }
-  }
-  return {v, j};
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-
 __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshold_passes) {
   extern __shared__ double s_dyn[];
   const int cap = prm.cap, ic = prm.inst_cap, lane = threadIdx.x;
@@ -293,7 +264,7 @@ __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshol
           inst = a.gt_inst[row];
           if (!finite3(x, y, a.gt_xyz[row * 3 + 2])) st |= UD_TM_ST_NONFINITE;
           else if (inst < 0 || inst >= ic) st |= UD_TM_ST_RANGE;
-          else ok = dist_xy(x, y, ex, ey) <= range;
+          else ok = ud_dist_xy(x, y, ex, ey) <= range;
         }
       }
       const unsigned long long bal = __ballot(ok);
@@ -344,12 +315,12 @@ __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshol
         const double x0 = s_ox[oo], y0 = s_oy[oo];
         int best = 0x7FFFFFFF;
         for (int h = lane; h < nh; h += 64)
-          if (s_hid[h] == wid && !s_hcl[h] && dist_xy(x0, y0, s_hx[h], s_hy[h]) < th) { best = h; break; }
-        best = wave_min_i(best);
+          if (s_hid[h] == wid && !s_hcl[h] && ud_dist_xy(x0, y0, s_hx[h], s_hy[h]) < th) { best = h; break; }
+        best = ud_wave_min(best);
         if (best != 0x7FFFFFFF && lane == 0) {
           s_hcl[best] = 1;
           s_omatch[oo] = best;
-          s_od[oo] = dist_xy(x0, y0, s_hx[best], s_hy[best]);
+          s_od[oo] = ud_dist_xy(x0, y0, s_hx[best], s_hy[best]);
         }
         __syncthreads();
       }
@@ -361,7 +332,7 @@ __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshol
       if (s_omatch[o] < 0) {
         const double x0 = s_ox[o], y0 = s_oy[o];
         for (int h = 0; h < nh; ++h)
-          if (!s_hcl[h] && dist_xy(x0, y0, s_hx[h], s_hy[h]) < th) { deg = 1; s_hadm[h] = 1; }
+          if (!s_hcl[h] && ud_dist_xy(x0, y0, s_hx[h], s_hy[h]) < th) { deg = 1; s_hadm[h] = 1; }
       }
       s_oadm[o] = (unsigned char)deg;
     }
@@ -407,21 +378,21 @@ __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshol
           int bestj = 0x7FFFFFFF;
           for (int j = lane; j < nb; j += 64) {
             if (s_used[j]) continue;
-            const double d = dist_xy(x0, y0, cx[ci[j]], cy[ci[j]]);
+            const double d = ud_dist_xy(x0, y0, cx[ci[j]], cy[ci[j]]);
             const double cur = (d < th ? d : big) - ui0 - s_v[j];
             double mv = s_minv[j];
             if (cur < mv) { mv = cur; s_minv[j] = cur; s_way[j] = j0; }
             if (mv < bestv) { bestv = mv; bestj = j; }
           }
-          const WaveMin w = wave_min_pair(bestv, bestj);     // equal reduced costs: the lowest column
-          if (w.j == 0x7FFFFFFF) break;
-          const double delta = w.v;
+          ud_wave_min_pair(bestv, bestj);                    // equal reduced costs: the lowest column
+          if (bestj == 0x7FFFFFFF) break;
+          const double delta = bestv;
           for (int j = lane; j < nb; j += 64) {
             if (s_used[j]) { s_u[s_p[j]] += delta; s_v[j] -= delta; }
             else s_minv[j] -= delta;
           }
           if (lane == 0) s_u[i] += delta;
-          j0 = w.j;
+          j0 = bestj;
           __syncthreads();
           if (s_p[j0] < 0) { found = true; break; }
         }
@@ -438,7 +409,7 @@ __global__ __launch_bounds__(64) void k_tm_walk(Ptrs a, Params prm, int threshol
       for (int j = lane; j < nb; j += 64) {
         const int i = s_p[j];
         if (i < 0) continue;
-        const double d = dist_xy(rx[ri[i]], ry[ri[i]], cx[ci[j]], cy[ci[j]]);
+        const double d = ud_dist_xy(rx[ri[i]], ry[ri[i]], cx[ci[j]], cy[ci[j]]);
         if (d < th) {
           const int o = obj_rows ? ri[i] : ci[j], h = obj_rows ? ci[j] : ri[i];
           s_omatch[o] = h;
@@ -517,13 +488,13 @@ __global__ __launch_bounds__(256) void k_tm_keys(const double* __restrict__ msco
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   if (g >= G) return;
   const double s = mscore[g];
-  keys[g] = s == s ? descending_bits(s + 0.0) : ~0ull;
+  keys[g] = s == s ? ud_desc_bits(s + 0.0) : ~0ull;
 }
 
 __global__ __launch_bounds__(256) void k_tm_thresholds(Ptrs a, Params prm) {
   __shared__ int s_wsum[4];
   __shared__ long long s_P;
-  const int t = blockIdx.x, c = prm.cls_of[t], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x, c = prm.cls_of[t], tid = threadIdx.x;
   const long long base = prm.seg[t], room = prm.seg[t + 1] - base;
   double* s = a.sorted + base;
   long long n = 0;
@@ -539,21 +510,13 @@ __global__ __launch_bounds__(256) void k_tm_thresholds(Ptrs a, Params prm) {
         ok = v == v;
       }
     }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) s_wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      before += w < wave ? s_wsum[w] : 0;
-      total += s_wsum[w];
-    }
+    const UdBlockRank cr = ud_block_rank<4>(ok, s_wsum);
     if (ok) {
-      const long long pos = n + before + __popcll(bal & ((1ull << lane) - 1ull));
+      const long long pos = n + cr.rank();
       if (pos < room) s[pos] = v;
       else st |= UD_TM_ST_RANGE;
     }
-    n += total;
+    n += cr.total;
     __syncthreads();
   }
   if (n > room) n = room;

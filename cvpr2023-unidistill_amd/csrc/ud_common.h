@@ -119,4 +119,26 @@ __device__ __forceinline__ int ud_wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+
+// Minimum over the 64 lanes of a wave; every lane gets it.
+__device__ __forceinline__ int ud_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+// Lexicographic minimum of (v, j) over the 64 lanes, in place in every lane: among equal v the lowest j wins.
+__device__ __forceinline__ void ud_wave_min_pair(double& v, int& j) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o);
+    const int oj = __shfl_xor(j, o);
+    if (ov < v || (ov == v && oj < j)) { v = ov; j = oj; }
+  }
+}
+
+// Planar distance in float64, as the evaluation stages write it: sqrt(dx * dx + dy * dy) of the a - b differences.
+__device__ __forceinline__ double ud_dist_xy(double ax, double ay, double bx, double by) {
+  const double dx = ax - bx, dy = ay - by;
+  return sqrt(dx * dx + dy * dy);
+}
 #endif

@@ -319,3 +319,48 @@ def test_fuse_pred_dicts(hip_lib):
         assert n == len(ref[b]["rows"]) and pds[b]["pred_boxes"].shape == (n, box_dim)
         assert torch.equal(pds[b]["pred_boxes"], want[0][b, :n]) and torch.equal(pds[b]["pred_scores"], want[1][b, :n])
         assert torch.equal(pds[b]["pred_labels"], want[2][b, :n])
+
+
+def _dense_boxes(n):
+    """n boxes of one label drawn so densely (four square metres of ground per box) that greedy NMS at THR drops about three in
+    ten; the last one lies almost on the first."""
+    rng = np.random.default_rng(100 + n)
+    half = max(1.0, 0.5 * np.sqrt(4.0 * n))
+    b = np.zeros((n, 7), np.float32)
+    b[:, 0:2] = rng.uniform(-half, half, (n, 2))
+    b[:, 2] = rng.uniform(-1, 1, n)
+    b[:, 3:6] = rng.uniform(1.0, 4.5, (n, 3))
+    b[:, 6] = rng.uniform(-3.1, 3.1, n)
+    if n > 1:
+        b[n - 1] = b[0]
+        b[n - 1, 0] += 0.1
+    return b
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 4096, 4100])
+def test_nms_keep_list_is_the_set_of_fusion_anchors(hip_lib, n):
+    """The one-wave NMS scan (csrc/nms_scan.h) has an instantiation in ud_nms_rotated_bev and one in box fusion: on one label,
+    strictly descending scores and one identity source both walk the same boxes in the same order, so the anchors of the fused
+    clusters are the NMS keep list and every box is a member of exactly one cluster.  n crosses a mask word (64 / 65) and a
+    lane's first word (4096 / 4100).  On the CPU, with the reference's IoU: box 0 is kept whatever follows, so every box that it
+    overlaps by more than THR is suppressed -- the last one at least: neither set is empty."""
+    from unidistill_amd.ops import nms
+    boxes = _dense_boxes(n)
+    scores = np.linspace(0.9, 0.1, n, dtype=np.float32)
+    assert n == 1 or (np.diff(scores) < 0).all()
+    first = [float(x) for x in boxes[0]]
+    iou0 = np.array([R.iou_bev64(first, [float(x) for x in boxes[j]]) for j in range(1, n)])
+    thr32 = float(np.float32(THR))
+    assert (np.abs(iou0 - thr32) >= MIN_MARGIN).all()
+    under_first = 1 + np.flatnonzero(iou0 > thr32)
+    assert n == 1 or under_first[-1] == n - 1
+
+    kept, count = nms._run(torch.from_numpy(boxes).cuda(), THR)
+    keep = kept[:int(count.item())].cpu().numpy()
+    assert keep[0] == 0 and not np.isin(under_first, keep).any()
+    got, num = run((boxes[None], scores[None], np.ones((1, n), np.int64), np.array([n], np.int32)), 1, iou_threshold=THR,
+                   max_out=n)
+    anchor, members = got[4][0], got[5][0]
+    assert num == [len(keep)]
+    assert np.array_equal(np.sort(anchor[:num[0]]), keep)
+    assert int(members.sum()) == n
