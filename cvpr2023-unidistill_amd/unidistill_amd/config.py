@@ -28,6 +28,15 @@ LIDAR_ENCODER = dict(point_cloud_range=POINT_CLOUD_RANGE, voxel_size=VOXEL_SIZE,
                      max_num_points=10, max_voxels=(120000, 160000), src_num_point_features=5,
                      use_num_point_features=5, map_to_bev_num_features=256)
 
+# PointPillars branch (layers/pillars.py): 0.6 m pillars over the whole height -> the 180 x 180 x 1 grid the BEV
+# trunk already takes (the sparse encoder reaches it at out_size_factor 8); one PFN layer of 256 channels = BEV_ENCODER's input
+PILLAR_ENCODER = dict(type="pillars", point_cloud_range=POINT_CLOUD_RANGE,
+                      voxel_size=[VOXEL_SIZE[0] * OUT_SIZE_FACTOR, VOXEL_SIZE[1] * OUT_SIZE_FACTOR,
+                                  POINT_CLOUD_RANGE[5] - POINT_CLOUD_RANGE[2]],
+                      grid_size=[GRID_SIZE[0] // OUT_SIZE_FACTOR, GRID_SIZE[1] // OUT_SIZE_FACTOR, 1], max_num_points=20,
+                      max_voxels=(30000, 40000), src_num_point_features=5, use_num_point_features=5, num_filters=[256],
+                      use_absolute_xyz=True, with_distance=False)
+
 CAMERA_ENCODER = dict(
     x_bound=[POINT_CLOUD_RANGE[0], POINT_CLOUD_RANGE[3], VOXEL_SIZE[0] * OUT_SIZE_FACTOR],
     y_bound=[POINT_CLOUD_RANGE[1], POINT_CLOUD_RANGE[4], VOXEL_SIZE[1] * OUT_SIZE_FACTOR],
@@ -61,9 +70,15 @@ DET_HEAD = dict(
                   nms_iou_threshold_test=0.1, nms_pre_max_size_test=1500, nms_post_max_size_test=100))
 
 
-def model_cfg(lidar=True, camera=True, iou_mode=None):
-    """iou_mode: None / "reference" = the reference's IoU terms; "rotated3d" = the rotated 3-D IoU in the head's loss."""
-    cfg = dict(class_names=CLASS_NAMES, lidar_encoder=copy.deepcopy(LIDAR_ENCODER) if lidar else None,
+LIDAR_ENCODERS = {"sparse": LIDAR_ENCODER, "pillars": PILLAR_ENCODER}
+
+
+def model_cfg(lidar=True, camera=True, iou_mode=None, lidar_encoder="sparse"):
+    """iou_mode: None / "reference" = the reference's IoU terms; "rotated3d" = the rotated 3-D IoU in the head's loss.
+    lidar_encoder: "sparse" (VoxelResBackBone8x, the reference's experiments) or "pillars" (PILLAR_ENCODER)."""
+    if lidar_encoder not in LIDAR_ENCODERS:
+        raise ValueError(f"lidar_encoder: expected one of {sorted(LIDAR_ENCODERS)}, got {lidar_encoder!r}")
+    cfg = dict(class_names=CLASS_NAMES, lidar_encoder=copy.deepcopy(LIDAR_ENCODERS[lidar_encoder]) if lidar else None,
                camera_encoder=copy.deepcopy(CAMERA_ENCODER) if camera else None,
                bev_encoder=copy.deepcopy(BEV_ENCODER), det_head=copy.deepcopy(DET_HEAD))
     if iou_mode is not None:

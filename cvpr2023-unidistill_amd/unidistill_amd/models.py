@@ -14,6 +14,7 @@ from .layers.bev import BevEncoder, FusionEncoder
 from .layers.center_head import CenterHeadIouAware, FCOSAssigner
 from .layers.gen_proposals import IouAwareGenProposals
 from .layers.lidar import LidarEncoder
+from .layers.pillars import PillarLidarEncoder
 from .layers.lss_fpn import LSSFPN
 from .ops.distill import feature_tap
 
@@ -75,6 +76,17 @@ class DetHead(nn.Module):
         return ret
 
 
+LIDAR_ENCODER_CLASSES = {"sparse": LidarEncoder, "pillars": PillarLidarEncoder}
+
+
+def lidar_encoder_class(cfg):
+    """The encoder class a lidar_encoder cfg asks for by its optional 'type' key; without one, LidarEncoder."""
+    kind = (cfg.get("type", "sparse") if isinstance(cfg, dict) else getattr(cfg, "type", "sparse"))
+    if kind not in LIDAR_ENCODER_CLASSES:
+        raise ValueError(f"lidar_encoder type: expected one of {sorted(LIDAR_ENCODER_CLASSES)}, got {kind!r}")
+    return LIDAR_ENCODER_CLASSES[kind]
+
+
 class BEVFusionCenterHead(nn.Module):
     """forward(lidar_points, cameras_imgs, metas, gt_boxes, return_feature=False)
 
@@ -93,7 +105,7 @@ class BEVFusionCenterHead(nn.Module):
         self.num_class = len(self.class_names)
         lidar_kwargs = {**(model_cfg.get("lidar_encoder_kwargs") or {}), **(lidar_kwargs or {})}
         camera_kwargs = {**(model_cfg.get("camera_encoder_kwargs") or {}), **(camera_kwargs or {})}
-        self.lidar_encoder = (LidarEncoder(model_cfg["lidar_encoder"], **lidar_kwargs)
+        self.lidar_encoder = (lidar_encoder_class(model_cfg["lidar_encoder"])(model_cfg["lidar_encoder"], **lidar_kwargs)
                               if model_cfg.get("lidar_encoder") else None)
         self.camera_encoder = (CameraEncoder(model_cfg["camera_encoder"], **camera_kwargs)
                                if model_cfg.get("camera_encoder") else None)

@@ -13,6 +13,8 @@ height_compression.py, the BEVFusion_*_exp files) import and run on this library
   iou3d_nms_cuda.boxes_iou3d_pairs                        -> ops.det_loss.rotated_iou3d (additive: nothing in the reference calls it)
   roiaware_pool3d_cuda.points_in_boxes_gpu                -> ops.gt_paste.points_in_boxes (ud_points_in_boxes)
   roiaware_pool3d_cuda, its other six names               -> import-time stubs (RoI-aware pooling: unused path; calling raises)
+  unidistill.layers.blocks_3d.det3d.vfe.pillar_vfe        -> layers.pillars.PillarVFE / PFNLayer (one PFN layer, ops/pillars.py)
+  unidistill.layers.blocks_2d.det3d.map_to_bev.pointpillar_scatter -> layers.pillars.PointPillarScatter
 Registry-style mmdet.core.* names the reference merely imports are provided as inert placeholders.
 """
 import sys
@@ -104,6 +106,10 @@ def install():
           **{n: _unavailable("roiaware_pool3d_cuda." + n) for n in (
               "points_in_boxes_cpu", "bev_in_boxes_cpu", "bev_in_boxes_gpu", "points_in_boxes_bev_gpu", "forward",
               "backward")})
+    # --- the PointPillars pair: pure PyTorch in the reference, one HIP pass here (a scatter fused with vfe.fuse(scatter))
+    from .layers import pillars
+    _leaf("unidistill.layers.blocks_3d.det3d.vfe.pillar_vfe", PillarVFE=pillars.PillarVFE, PFNLayer=pillars.PFNLayer)
+    _leaf("unidistill.layers.blocks_2d.det3d.map_to_bev.pointpillar_scatter", PointPillarScatter=pillars.PointPillarScatter)
     # --- spconv
     _module("spconv")
     _module("spconv.core", ConvAlgo=sp.ConvAlgo)

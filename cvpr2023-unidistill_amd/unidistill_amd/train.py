@@ -21,11 +21,13 @@ from .models import BEVFusionCenterHead
 from .ops import distill as D, wgrad_stream
 
 
-def build_model(modality, iou_mode=None, frozen_bn=False, frozen_encoder=False, **kw):
+def build_model(modality, iou_mode=None, frozen_bn=False, frozen_encoder=False, lidar_encoder="sparse", **kw):
     """modality: 'camera' | 'lidar' | 'fusion' -> BEVFusionCenterHead.
+    lidar_encoder: 'sparse' (the reference's VoxelResBackBone8x) or 'pillars' (layers/pillars.py, config.PILLAR_ENCODER).
     frozen_bn / frozen_encoder: the reference's BaseEncoder switches (layers/base.py) -- True for every encoder of the model, or
     the encoders they apply to ('lidar', 'camera', or a collection of the two: the frozen LiDAR half of a fusion student)."""
-    cfg = C.model_cfg(lidar=modality in ("lidar", "fusion"), camera=modality in ("camera", "fusion"), iou_mode=iou_mode)
+    cfg = C.model_cfg(lidar=modality in ("lidar", "fusion"), camera=modality in ("camera", "fusion"), iou_mode=iou_mode,
+                      lidar_encoder=lidar_encoder)
     for flag, val in (("frozen_bn", frozen_bn), ("frozen_encoder", frozen_encoder)):
         which = ("lidar", "camera") if val is True else ((val,) if isinstance(val, str) else tuple(val or ()))
         if set(which) - {"lidar", "camera"}:

@@ -1559,6 +1559,58 @@ int ud_track_interp_fill(const double* pred_rec, const int32_t* pred_cls, const 
                          int32_t* out_gt_key, int32_t* out_gt_src, int32_t* status, void* workspace, size_t workspace_bytes,
                          ud_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* PointPillars encoder: PillarVFE (one PFNLayer, use_norm, last_layer) +     */
+/* PointPillarScatter -- csrc/pillars.hip, DESIGN 2.26                        */
+/*   layers/blocks_3d/det3d/vfe/pillar_vfe.py:8-145                           */
+/*   layers/blocks_2d/det3d/map_to_bev/pointpillar_scatter.py:5-40            */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * Inputs of all three passes: the voxelizer's output on a one-cell-high grid,
+ *   voxels f32[M,P,F] (rows >= num[m] zero)   coords i32[M,4] (b,z,y,x)   num i32[M]   weight f32[C,K]
+ * The K row features are never stored: the raw row (its columns 3.. only without UD_PILLAR_ABS_XYZ), xyz - mean_xyz (sum over
+ * the P rows / num), xyz - cell centre (coords * voxel_size + offset, fp32), ||xyz|| with UD_PILLAR_DISTANCE; all times
+ * (row < num).  K = F + 6 (F + 3 without UD_PILLAR_ABS_XYZ) (+ 1).  geom: HOST f32[6] = voxel_size xyz, offset xyz
+ * (voxel_size / 2 + range minimum, evaluated in double by the caller as the reference does).
+ * Supported: C % 32 == 0, C <= 256; 3 <= F <= 8; 1 <= P <= 64.  fp32, no float atomics, every sum in a fixed order.
+ */
+#define UD_PILLAR_ABS_XYZ 1u
+#define UD_PILLAR_DISTANCE 2u
+
+/* Scratch of ud_pillar_stats / ud_pillar_bwd for these sizes; 0 for unsupported sizes. */
+size_t ud_pillar_workspace_bytes(int M, int P, int F, int C, unsigned flags);
+
+/*
+ * Training statistics of z = weight . feat over ALL M * P rows (padded rows count, with z = 0: what the reference's
+ * BatchNorm1d sees): stats f32[4,C] = mean, invstd (biased variance + eps), scale = gamma * invstd, shift = beta - mean * scale.
+ * running_mean / running_var (NULL to skip): (1 - momentum) * old + momentum * (mean | unbiased variance, n = M * P).
+ */
+int ud_pillar_stats(const float* voxels, const int32_t* coords, const int32_t* num, int M, int P, int F,
+                    const float* weight, int C, unsigned flags, const float* geom, const float* gamma, const float* beta,
+                    float eps, float momentum, float* running_mean, float* running_var, float* stats, void* workspace,
+                    size_t workspace_bytes, ud_stream_t stream);
+
+/*
+ * out[m,c] = max over the P rows of relu(z * scale[c] + shift[c]) (padded rows give relu(shift[c])), written to
+ * bev f32[B,ny,nx,C] at (coords b, y, x); bev is zero-filled here first.  pillars f32[M,C] and argmax u8[M,C] (the first row
+ * that attains the maximum) are optional (NULL).  A pillar whose coordinates fall outside the map is not written.
+ */
+int ud_pillar_apply(const float* voxels, const int32_t* coords, const int32_t* num, int M, int P, int F,
+                    const float* weight, int C, unsigned flags, const float* geom, const float* scale, const float* shift,
+                    int B, int ny, int nx, float* bev, float* pillars, uint8_t* argmax, ud_stream_t stream);
+
+/*
+ * Backward of the two passes above for dbev f32[B,ny,nx,C] (plus dpillars f32[M,C], the gradient of the optional pillars
+ * output, or NULL): dweight f32[C,K], dgamma / dbeta f32[C] (each NULL to skip).
+ * stats / argmax: what the forward used (frozen != 0: stats = running mean, 1 / sqrt(running var + eps), folded scale, shift,
+ * and dz = scale * dy on the argmax rows only; otherwise the batch-statistics backward, whose dz is non-zero on every row).
+ */
+int ud_pillar_bwd(const float* voxels, const int32_t* coords, const int32_t* num, int M, int P, int F, const float* weight,
+                  int C, unsigned flags, const float* geom, const float* dbev, const float* dpillars, int B, int ny, int nx,
+                  const uint8_t* argmax, const float* stats, int frozen, float* dweight, float* dgamma, float* dbeta, void* workspace,
+                  size_t workspace_bytes, ud_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
